@@ -10,14 +10,21 @@ rank), no data-path collective; the value is the sum of bytes over the max of
 the per-rank times.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c5]
+                  [--dump-outputs DIR] [--full]
 
 With --gpus N > 1 and no torchrun environment, this process starts N rank
 processes itself (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set per child)
 before anything touches a GPU, and exits with their status; under
 `torch.distributed.run` each rank reads those variables from the environment.
 
-Besides the headline `value` (chunk ids = rolling hash, as BASELINE's metric
-names), the same line carries, driver-observed:
+A plain run measures the headline only: it fills the stream, warms up, times
+the K steps and prints the result line (`value`, `ms_per_step`, the stage times
+and the roofline fraction of those same steps).  --dump-outputs DIR also writes
+the records of the last timed step, field by field, as DIR/<name>.npy (see
+dump_outputs).  Everything else is measured only with --full.
+
+With --full, besides the headline `value` (chunk ids = rolling hash, as
+BASELINE's metric names), the same line carries, driver-observed:
   value_c3, value_c5
                BASELINE configs[2] and [4] (C3: two copies of 4 GiB; C5: all
                zeros) in the headline mode, timed as the headline
@@ -30,6 +37,9 @@ names), the same line carries, driver-observed:
                96-155), with liblzo2 on one core beside it
   static_index the first GiB against 300 K and 2 M ids known by value only
                (an index loaded from earlier backups, chunk_index.cc:26-79)
+  cpu_baseline the oracle port on one core over a sample of the same stream
+(--no-extras, --no-cpu-baseline, --no-lzo and --sha1-steps 0 leave legs of a
+--full run out.)
 """
 import argparse
 import json
@@ -71,10 +81,20 @@ def parse(argv=None):
     ap.add_argument("--sha1-steps", type=int, default=5)
     ap.add_argument("--sha1", action="store_true",
                     help="the headline itself with SHA-1 chunk ids (ZC_FLAG_SHA1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other leg (C3/C5, SHA-1 ids, incremental and seeded repositories, "
+                         "end to end, feed, bundle_lzo, static_index, the CPU baseline); off: the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the records of the last timed step as DIR/<name>.npy")
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU rehearsal of the launch and rank bookkeeping: each rank chunks its "
                          "stream with the oracle instead of the GPU (no measurement)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if not args.full:
+        # a plain run is the headline alone
+        args.no_extras = True
+        args.no_cpu_baseline = True
+    return args
 
 
 # --------------------------------------------------------------------------
@@ -517,6 +537,39 @@ def bundle_leg(torch, buf, n, recs, world, local, cpu_sample):
     return res
 
 
+# --dump-outputs keeps at most this many records (104 bytes each as written:
+# under 64 MB in all); a longer record list is sampled at fixed seeded indices
+DUMP_MAX_RECORDS = 500000
+
+
+def dump_outputs(out_dir, recs, prefix=""):
+    """What a caller of the timed path receives from its last step -- the
+    stream's records (BackupCreator.records()) -- one array per field as
+    out_dir/<prefix><name>.npy, every value exact in its float type:
+      count       float64 (1,)     records of the stream
+      index       float64 (m,)     which records the other arrays hold (all of
+                                   them, or a fixed seeded sample in stream order)
+      offset, size, kind           float64 (m,)
+      rolling_hi, rolling_lo       float64 (m,)  the 64-bit rolling hash's halves
+      sha1        float32 (m, 16)  the ChunkId's SHA-1 prefix, byte by byte"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    idx = np.arange(len(recs))
+    if len(recs) > DUMP_MAX_RECORDS:
+        idx = np.sort(np.random.default_rng(0).choice(len(recs), DUMP_MAX_RECORDS, replace=False))
+    r = recs[idx]
+    arrays = {"count": np.array([len(recs)], dtype=np.float64),
+              "index": idx.astype(np.float64),
+              "offset": r["offset"].astype(np.float64),
+              "size": r["size"].astype(np.float64),
+              "kind": r["kind"].astype(np.float64),
+              "rolling_hi": (r["rolling"] >> np.uint64(32)).astype(np.float64),
+              "rolling_lo": (r["rolling"] & np.uint64(0xFFFFFFFF)).astype(np.float64),
+              "sha1": r["sha1"].astype(np.float32)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{prefix}{name}.npy"), a)
+
+
 def stage_dict(st):
     return {"scan_ms": round(st["scan_ms"], 4), "resolve_ms": round(st["resolve_ms"], 4),
             "total_ms": round(st["total_ms"], 4), "anchors": st["anchors"],
@@ -654,6 +707,8 @@ def run_rank(args):
     recs = bc.records().copy()
     nrec = len(recs)
     bc.close()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, recs, f"rank{rank}_" if world > 1 else "")
     ms_step = elapsed / args.steps * 1e3
     value = job_value(n, world, args.steps, elapsed)
     scan_avg = sum(scan_ms) / len(scan_ms)

@@ -50,6 +50,6 @@ if [ -z "$NO_LZO" ] && [ -x tools/ubench/lzo_dict_bench ]; then
 fi
 (lscpu; echo; echo "nproc: $(nproc)") > "$OUT/host_cpu.txt"
 if [ -z "$NO_BENCH" ]; then
-  timeout -k 10 300 python3 bench.py > "$OUT/bench.jsonl" 2> "$OUT/bench.err"
+  timeout -k 10 300 python3 bench.py --full > "$OUT/bench.jsonl" 2> "$OUT/bench.err"
 fi
 echo done
