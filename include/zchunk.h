@@ -39,6 +39,9 @@
  *   zc_chunk_device        the same stream already resident in HBM (feed + finish in one call)
  *   zc_chunk_host          the same stream in host memory, copy overlapped with the scan
  *                          (the read loop of zutils.cc:100-124 + finish in one call)
+ *   zc_lzo_frame_info      the frame NoStreamAndUnknownSizeDecoder reads    compression.cc:369-402
+ *   zc_bundle_scatter      Bundle::Reader::get for every chunk a restore emits  bundle.cc:235-251
+ *   zc_parse_instructions  the Message::parse loop of restore()  backup_restorer.cc:38-107
  *   zc_last_error          the DEF_EX exceptions / CHECK aborts of the reference
  *                          (backup_creator.cc:112,165-166, chunk_index.hh:88-89)
  */
@@ -241,6 +244,7 @@ const void* zc_stream_data(const zc_ctx* ctx, uint64_t offset, size_t n);
  * written, or needed (ZC_ERR_ARG) when cap is too small */
 int zc_serialize_records(const zc_ctx* ctx, const zc_record* recs, size_t n, void* out, size_t cap,
                          size_t* n_out);
+/* (ctx NULL: the message of the calling thread's last failed call that takes no context) */
 const char* zc_last_error(const zc_ctx* ctx);
 
 /* synthetic seeded stream on the device (tests / benchmarks): byte k is byte
@@ -295,6 +299,43 @@ int zc_adler32(zc_ctx* ctx, const void* d_base, const uint64_t* off, const uint6
                uint32_t* out);
 /* device time of the last zc_lzo_compress's parse kernel (ms) and its 48 KiB blocks */
 int zc_lzo_last_stats(const zc_ctx* ctx, double* parse_ms, uint64_t* blocks);
+
+/* ---- Restore: replaying a BackupInstruction stream over decoded bundles ----
+ * restore() (backup_restorer.cc:38-107) parses the instruction stream and, per chunk_to_emit,
+ * copies the chunk out of its bundle's decoded payload (Bundle::Reader::get, bundle.cc:235-251);
+ * per bytes_to_emit it appends the bytes.  Here: the parse (host), the frame a bundle's lzo1x
+ * stream is stored under (host), and the copies on the device, HBM to HBM.  The decoding of
+ * the lzo1x stream itself is the caller's (liblzo2's lzo1x_decompress_safe, as the reference
+ * calls it: compression.cc:472-490).  Callers detect these entry points by their symbols (the
+ * ABI version stays 5).
+ *
+ * The codes of a framed bundle beside liblzo2's own (-4 .. -8): */
+#define ZC_LZO_E_FRAME (-100) /* fewer than 16 bytes, or 16 + csize > in_size */
+#define ZC_LZO_E_SIZE  (-101) /* stream ok, but decoded size != the frame's size */
+/* the frame's two sizes (host memory; no device work): ZC_OK, or ZC_LZO_E_FRAME */
+int zc_lzo_frame_info(const void* framed, size_t avail, uint64_t* payload_size, uint64_t* compressed_size);
+/* The inverse of zc_bundle_gather (Bundle::Reader::get, bundle.cc:235-251, for every chunk a
+ * restore emits): extent i, d_src[src_off[i] ..+ sizes[i]), goes to d_dst + dst_off[i].  One source
+ * extent may go to many destinations (a chunk emitted more than once). */
+int zc_bundle_scatter(zc_ctx* ctx, const void* d_src, const uint64_t* src_off, const uint64_t* sizes,
+                      size_t n, void* d_dst, const uint64_t* dst_off);
+/* One entry per chunk_to_emit / bytes_to_emit of a BackupInstruction stream, in the order
+ * restore() acts on them (an instruction's chunk before its bytes). */
+enum { ZC_INSTR_CHUNK = 0, ZC_INSTR_BYTES = 1 };
+typedef struct {
+  uint32_t kind;      /* ZC_INSTR_CHUNK / ZC_INSTR_BYTES */
+  uint8_t id[24];     /* CHUNK: ChunkId::toBlob (chunk_id.cc:19-27) */
+  uint32_t reserved;
+  uint64_t data_off;  /* BYTES: offset of the raw bytes inside the stream given */
+  uint64_t size;      /* BYTES: their count */
+} zc_instruction;
+/* The inverse of zc_serialize_records (Message::parse, message.cc:24-42; zbackup.proto:149-159):
+ * each message is a varint32 length plus fields 1 (chunk_to_emit, 24 bytes) and/or 2
+ * (bytes_to_emit), in either order, each at most once.  *n_out = the entries found; ZC_ERR_ARG
+ * (message in zc_last_error(NULL), per thread) when cap is smaller, or on anything else: a
+ * truncated varint, a length past the end, another field number, a chunk blob that is not 24
+ * bytes.  Host memory only. */
+int zc_parse_instructions(const void* data, size_t n, zc_instruction* out, size_t cap, size_t* n_out);
 
 int zc_abi_version(void);
 /* digest of the sources this library was built from (zbackup_amd/_build.py

@@ -14,6 +14,7 @@ SOURCES = [os.path.join(CSRC, "zc_kernels.hip"), os.path.join(CSRC, "zc_engine.c
 # host-only sources (no device code; built by the host compiler with x86 intrinsics)
 HOST_ONLY = {"zc_sha256.cpp"}
 HEADERS = [os.path.join(CSRC, "zc_device.h"), os.path.join(CSRC, "zc_lzo_core.h"),
+           os.path.join(CSRC, "zc_lzo_dec.h"),
            os.path.join(ROOT, "include", "zchunk.h")]
 ARCH = os.environ.get("ZC_OFFLOAD_ARCH", "gfx950")
 

@@ -20,7 +20,10 @@ EXPORTS = ["zc_create", "zc_destroy", "zc_seed_index", "zc_get_input_buffer",
            "zc_last_error", "zc_fill_splitmix64", "zc_abi_version", "zc_read_stream", "zc_chunk_host",
            "zc_forget_stream_chunks", "zc_set_window", "zc_get_window", "zc_take_records", "zc_sha256_create", "zc_sha256_add", "zc_sha256_finish", "zc_sha256_destroy", "zc_sha256_impl",
            "zc_bundle_plan", "zc_bundle_gather", "zc_lzo_capacity", "zc_lzo_compress", "zc_lzo_compress_host", "zc_lzo_last_stats", "zc_adler32", "zc_serialize_records", "zc_stream_data", "zc_build_id",
-           "zc_seed_index_meta", "zc_export_chunk_meta", "zc_anchor_def"]
+           "zc_seed_index_meta", "zc_export_chunk_meta", "zc_anchor_def",
+           "zc_lzo_frame_info", "zc_bundle_scatter", "zc_parse_instructions"]
+ZC_LZO_E_FRAME, ZC_LZO_E_SIZE = -100, -101
+ZC_INSTR_CHUNK, ZC_INSTR_BYTES = 0, 1
 ZC_META_NO_ANCHOR = 0xFFFFFFFF
 
 
@@ -38,6 +41,11 @@ class ZcChunkMeta(ctypes.Structure):
     _fields_ = [("sha1", ctypes.c_uint8 * 16), ("rolling", ctypes.c_uint64), ("size", ctypes.c_uint32),
                 ("anchor_def", ctypes.c_uint32), ("anchor", ctypes.c_uint32), ("gear", ctypes.c_uint32),
                 ("fingerprint", ctypes.c_uint64)]
+
+
+class ZcInstruction(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_uint32), ("id", ctypes.c_uint8 * 24), ("reserved", ctypes.c_uint32),
+                ("data_off", ctypes.c_uint64), ("size", ctypes.c_uint64)]
 
 
 class ZcStats(ctypes.Structure):
@@ -120,6 +128,10 @@ def load(path=LIB_PATH):
         "zc_seed_index_meta": (i32, [vp, vp, sz, vp, sz]),
         "zc_export_chunk_meta": (i32, [vp, vp, sz, ctypes.POINTER(sz)]),
         "zc_anchor_def": (u32, [u32]),
+        # restore: the bundle frame, chunk scatter, instruction parsing
+        "zc_lzo_frame_info": (i32, [vp, sz, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
+        "zc_bundle_scatter": (i32, [vp, vp, vp, vp, sz, vp, vp]),
+        "zc_parse_instructions": (i32, [vp, sz, vp, sz, ctypes.POINTER(sz)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

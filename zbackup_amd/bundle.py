@@ -5,6 +5,11 @@
   Bundle::Creator::write    -> lzo1x_1 compression    bundle.cc:120-151,
                                framing                compression.cc:435-466, 586-606
 
+For the read side: `BundleCompressor.scatter` is Bundle::Reader::get for every
+chunk a restore emits (bundle.cc:235-251), `parse_backup_data` the instruction
+parse of restore() (backup_restorer.cc:38-107), `frame_info` the frame a
+bundle's lzo1x stream is stored under (compression.cc:369-402).
+
 `plan_bundles` is host bookkeeping; `BundleCompressor.gather` and `.compress`
 run on the GPU through libzchunk.so (zc_bundle_gather / zc_lzo_compress);
 there is no CPU fallback.  Device buffers are passed as raw pointers (e.g. a
@@ -86,6 +91,14 @@ class BundleCompressor:
         _check(self._L, self._ctx, rc, "zc_lzo_compress_host")
         return [out[int(o):int(o) + int(s)].tobytes() for o, s in zip(out_off, out_size)]
 
+    def scatter(self, d_src, src_off, sizes, d_dst, dst_off):
+        """The inverse of gather: extent i, d_src[src_off[i] ..+ sizes[i]), to
+        d_dst + dst_off[i]; one extent may go to many places."""
+        src_off, sizes, dst_off = _u64(src_off), _u64(sizes), _u64(dst_off)
+        rc = self._L.zc_bundle_scatter(self._ctx, d_src, src_off.ctypes.data, sizes.ctypes.data, len(sizes), d_dst,
+                                       dst_off.ctypes.data)
+        _check(self._L, self._ctx, rc, "zc_bundle_scatter")
+
     def adler32(self, d_base, off, length):
         """zlib adler32 (from 1) of each device range d_base[off[i] ..+ length[i])."""
         off, length = _u64(off), _u64(length)
@@ -116,3 +129,41 @@ class BundleCompressor:
             self.close()
         except Exception:
             pass
+
+
+INSTRUCTION_DTYPE = np.dtype([("kind", "<u4"), ("id", "u1", (24,)), ("reserved", "<u4"), ("data_off", "<u8"),
+                              ("size", "<u8")])
+assert INSTRUCTION_DTYPE.itemsize == ctypes.sizeof(_lib.ZcInstruction)
+
+
+def _host_check(L, rc, what):
+    if rc != _lib.ZC_OK:
+        msg = L.zc_last_error(None) or b""
+        raise _lib.ZcError(f"{what} failed ({rc}): {msg.decode(errors='replace')}")
+
+
+def parse_backup_data(data):
+    """A BackupInstruction stream (BackupCreator.get_backup_data()) as a
+    structured array (INSTRUCTION_DTYPE), one entry per chunk_to_emit
+    (ZC_INSTR_CHUNK, `id`) and bytes_to_emit (ZC_INSTR_BYTES, the bytes are
+    data[data_off ..+ size)), in the order restore() acts on them."""
+    L = _lib.load()
+    data = bytes(data)
+    n = ctypes.c_size_t()
+    out = np.zeros(len(data) // 2 + 1, dtype=INSTRUCTION_DTYPE)  # an entry takes at least two bytes
+    rc = L.zc_parse_instructions(data, len(data), out.ctypes.data, len(out), ctypes.byref(n))
+    _host_check(L, rc, "zc_parse_instructions")
+    return out[:n.value].copy()
+
+
+def frame_info(framed):
+    """(payload size, compressed size) of a framed bundle's first 16 bytes;
+    raises on a frame the decoder would refuse."""
+    L = _lib.load()
+    framed = bytes(framed)
+    n, cz = ctypes.c_uint64(), ctypes.c_uint64()
+    rc = L.zc_lzo_frame_info(framed, len(framed), ctypes.byref(n), ctypes.byref(cz))
+    if rc == _lib.ZC_LZO_E_FRAME:
+        raise _lib.ZcError(f"zc_lzo_frame_info: bad frame ({rc}) in {len(framed)} bytes")
+    _host_check(L, rc, "zc_lzo_frame_info")
+    return n.value, cz.value

@@ -491,4 +491,8 @@ hipError_t lzo_adler32(LzoScratch* s, const uint8_t* d_base, const uint64_t* off
 hipError_t lzo_compress(LzoScratch* s, const uint8_t* d_payload, const uint64_t* pay_off, const uint64_t* pay_size,
                         size_t n, uint8_t* d_out, const uint64_t* out_off, uint64_t* out_size, hipStream_t st);
 
+// restore: d_dst + dst_off[i] <- d_src[off[i] ..+ size[i]), the inverse of lzo_gather
+hipError_t lzo_scatter(LzoScratch* s, const uint8_t* d_src, const uint64_t* off, const uint64_t* size, size_t n,
+                       uint8_t* d_dst, const uint64_t* dst_off, hipStream_t st);
+
 }  // namespace zc

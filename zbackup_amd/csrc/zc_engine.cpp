@@ -51,6 +51,7 @@
 
 #include "../../include/zchunk.h"
 #include "zc_device.h"
+#include "zc_lzo_dec.h"
 
 using namespace zc;
 
@@ -3778,7 +3779,13 @@ int zc_serialize_records(const zc_ctx* c, const zc_record* recs, size_t n, void*
   return ZC_OK;
 }
 
-const char* zc_last_error(const zc_ctx* c) { return c ? c->err.c_str() : "null context"; }
+// the calls that take no context (zc_lzo_frame_info, zc_parse_instructions) leave
+// their message here, per thread, until the thread's next such call
+static thread_local std::string g_host_err;
+const char* zc_last_error(const zc_ctx* c) {
+  if (c) return c->err.c_str();
+  return g_host_err.empty() ? "null context" : g_host_err.c_str();
+}
 
 int zc_fill_splitmix64(void* d_data, uint64_t n, uint64_t seed, int device) {
   if (n && !d_data) return ZC_ERR_ARG;
@@ -3921,5 +3928,123 @@ int zc_lzo_last_stats(const zc_ctx* c, double* parse_ms, uint64_t* blocks) {
   const LzoTimes t = c->lzo ? *lzo_times(c->lzo) : LzoTimes{};
   if (parse_ms) *parse_ms = t.parse_ms;
   if (blocks) *blocks = t.blocks;
+  return ZC_OK;
+}
+
+// ---- restore: the frame of an lzo1x bundle (zc_lzo_dec.h), chunk scatter, instruction parsing ----
+
+static int host_arg_error(const char* msg) {
+  g_host_err = msg;
+  return ZC_ERR_ARG;
+}
+static int ctx_arg_error(zc_ctx* c, const char* msg) {
+  if (c)
+    c->err = msg;
+  else
+    g_host_err = msg;
+  return ZC_ERR_ARG;
+}
+
+static_assert(ZC_LZO_E_FRAME == zclzo::kFrameBad && ZC_LZO_E_SIZE == zclzo::kFrameSize, "frame codes");
+
+int zc_lzo_frame_info(const void* framed, size_t avail, uint64_t* payload_size, uint64_t* compressed_size) {
+  if ((avail && !framed) || !payload_size || !compressed_size)
+    return host_arg_error("zc_lzo_frame_info: null pointer");
+  g_host_err.clear();
+  uint32_t n = 0, csize = 0;
+  const int rc = zclzo::frame_read((const uint8_t*)framed, avail, &n, &csize);
+  if (rc) return rc;
+  *payload_size = n;
+  *compressed_size = csize;
+  return ZC_OK;
+}
+
+int zc_bundle_scatter(zc_ctx* c, const void* d_src, const uint64_t* src_off, const uint64_t* sizes, size_t n,
+                      void* d_dst, const uint64_t* dst_off) {
+  ZC_LOCK(c);
+  if (!c || (n && (!d_src || !src_off || !sizes || !d_dst || !dst_off)))
+    return ctx_arg_error(c, "zc_bundle_scatter: null pointer");
+  if (!n) return ZC_OK;
+  DeviceGuard g(c->device);
+  if (!c->lzo) c->lzo = lzo_scratch_new();
+  hipError_t e = hipEventRecord(c->ev_in, nullptr);
+  if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, c->ev_in, 0);
+  if (e == hipSuccess)
+    e = lzo_scatter(c->lzo, (const uint8_t*)d_src, src_off, sizes, n, (uint8_t*)d_dst, dst_off, c->stream);
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(c->stream);
+    return lzo_fail(c, e, "zc_bundle_scatter");
+  }
+  c->err.clear();
+  return ZC_OK;
+}
+
+// The inverse of zc_serialize_records: Message::parse per instruction
+// (message.cc:24-42: varint32 length, then the BackupInstruction's fields,
+// zbackup.proto:149-159), in the order restore() acts on them
+// (backup_restorer.cc:59-88: the chunk first, then the bytes).
+int zc_parse_instructions(const void* data, size_t n, zc_instruction* out, size_t cap, size_t* n_out) {
+  if ((n && !data) || (cap && !out) || !n_out) return host_arg_error("zc_parse_instructions: null pointer");
+  const uint8_t* p = (const uint8_t*)data;
+  size_t pos = 0, cnt = 0;
+  char msg[160];
+  // a varint of at most 32 bits' worth of 7-bit groups inside [pos, end)
+  auto varint = [&](size_t end, uint64_t* v) {
+    *v = 0;
+    for (int k = 0; k < 5; k++) {
+      if (pos >= end) return false;
+      const uint8_t b = p[pos++];
+      *v |= (uint64_t)(b & 0x7f) << (7 * k);
+      if (!(b & 0x80)) return *v <= 0xffffffffull;
+    }
+    return false;
+  };
+  auto bad = [&](const char* what, size_t at) {
+    snprintf(msg, sizeof msg, "zc_parse_instructions: %s at byte %zu", what, at);
+    *n_out = cnt;
+    return host_arg_error(msg);
+  };
+  while (pos < n) {
+    const size_t at = pos;
+    uint64_t len;
+    if (!varint(n, &len)) return bad("truncated or overlong length varint", at);
+    if (len > n - pos) return bad("instruction length past the end of the stream", at);
+    const size_t end = pos + (size_t)len;
+    bool has_chunk = false, has_bytes = false;
+    zc_instruction chunk{}, bytes{};
+    while (pos < end) {
+      const size_t fat = pos;
+      const uint8_t tag = p[pos++];
+      if (tag != 0x0a && tag != 0x12) return bad("a field other than chunk_to_emit / bytes_to_emit", fat);
+      uint64_t flen;
+      if (!varint(end, &flen)) return bad("truncated field length", fat);
+      if (flen > end - pos) return bad("field past the end of its instruction", fat);
+      if (tag == 0x0a) {
+        if (flen != 24) return bad("chunk_to_emit is not a 24-byte chunk id", fat);
+        if (has_chunk) return bad("chunk_to_emit twice in one instruction", fat);
+        has_chunk = true;
+        chunk.kind = ZC_INSTR_CHUNK;
+        memcpy(chunk.id, p + pos, 24);
+      } else {
+        if (has_bytes) return bad("bytes_to_emit twice in one instruction", fat);
+        has_bytes = true;
+        bytes.kind = ZC_INSTR_BYTES;
+        bytes.data_off = pos;
+        bytes.size = flen;
+      }
+      pos += (size_t)flen;
+    }
+    for (const zc_instruction* e : {has_chunk ? &chunk : nullptr, has_bytes ? &bytes : nullptr}) {
+      if (!e) continue;
+      if (cnt < cap) out[cnt] = *e;
+      cnt++;
+    }
+  }
+  *n_out = cnt;
+  if (cnt > cap) {
+    snprintf(msg, sizeof msg, "zc_parse_instructions: %zu entries, room for %zu", cnt, cap);
+    return host_arg_error(msg);
+  }
+  g_host_err.clear();
   return ZC_OK;
 }

@@ -17,7 +17,9 @@
 //                        staged encodings), 16-byte stores aligned on the
 //                        destination;
 //   zc_lzo_or_kernel     a final run of 1-3 literals or-ed into the last match.
-// The same copy kernel gathers chunk extents into bundle payloads.
+// The same copy kernel gathers chunk extents into bundle payloads and, for
+// restore, scatters decoded chunk extents and bytes_to_emit runs to their
+// places in the restored stream.
 #include <hip/hip_runtime.h>
 
 #include <stdlib.h>
@@ -296,6 +298,16 @@ hipError_t lzo_gather(LzoScratch* s, const uint8_t* d_src, const uint64_t* off, 
       list.push_back(Copy{d_src + off[i] + k, d_dst + pos + k, std::min(kPiece, size[i] - k)});
     pos += size[i];
   }
+  return lzo_copy_list(s, list, st);
+}
+
+hipError_t lzo_scatter(LzoScratch* s, const uint8_t* d_src, const uint64_t* off, const uint64_t* size, size_t n,
+                       uint8_t* d_dst, const uint64_t* dst_off, hipStream_t st) {
+  constexpr uint64_t kPiece = zclzo::kPiece;
+  std::vector<Copy> list;
+  for (size_t i = 0; i < n; i++)
+    for (uint64_t k = 0; k < size[i]; k += kPiece)
+      list.push_back(Copy{d_src + off[i] + k, d_dst + dst_off[i] + k, std::min(kPiece, size[i] - k)});
   return lzo_copy_list(s, list, st);
 }
 
