@@ -46,6 +46,7 @@
 #include "chunk_index.hh"
 #include "chunk_storage.hh"
 #include "config.hh"
+#include "encryption_key.hh"
 #include "message.hh"
 #include "nocopy.hh"
 #include "sptr.hh"
@@ -424,6 +425,217 @@ public:
     framed.resize( n );
     for ( size_t i = 0; i < n; ++i )
       framed[ i ].assign( out, outOff[ i ], outSize[ i ] );
+  }
+};
+
+/// Contexts for calls that come from several threads at once: one per thread
+/// that is inside a call at the moment, made on first need and reused after
+/// (what GpuLzoBundleCompressor keeps for itself, shared by the two classes below).
+class ZcContextPool: NoCopy
+{
+  int device;
+  std::mutex poolMutex;
+  std::vector< zc_ctx * > idle, all;
+
+public:
+  explicit ZcContextPool( int device_ ): device( device_ ) {}
+  ~ZcContextPool()
+  {
+    for ( size_t i = 0; i < all.size(); ++i )
+      zc_destroy( all[ i ] );
+  }
+
+  zc_ctx * acquire()
+  {
+    std::lock_guard< std::mutex > lock( poolMutex );
+    if ( !idle.empty() )
+    {
+      zc_ctx * c = idle.back();
+      idle.pop_back();
+      return c;
+    }
+    zc_ctx * c = 0;
+    zcCheck( zc_create( &c, 65536, device, 0 ), 0, "zc_create" );
+    all.push_back( c );
+    return c;
+  }
+
+  void release( zc_ctx * c )
+  {
+    std::lock_guard< std::mutex > lock( poolMutex );
+    idle.push_back( c );
+  }
+};
+
+/// The bundle FILE on the GPU, for Bundle::Creator::write (bundle.cc:96-155) in a
+/// repository with or without a password: what EncryptedFile::OutputStream makes
+/// of the bytes written through it (encrypted_file.cc:239-392) -- the random
+/// first block, both Adler-32s, PKCS#7 padding, AES-128-CBC from the zero IV
+/// under EncryptionKey::getKey().  write() serializes the two messages as it
+/// does today, but into a string, and hands the rest over:
+///
+///   string prefix, file;
+///   if ( key.hasKey() ) prefix.assign( randomBlock, 16 );  // Random::genaratePseudo, as writeRandomIv does
+///   { StringOutputStream s( &prefix ); CodedOutputStream c( &s );
+///     Message::serialize( header, c ); Message::serialize( info, c ); }
+///   sealer.seal( prefix, framed, file );   // framed: GpuLzoBundleCompressor's output
+///   UnbufferedFile( fileName, UnbufferedFile::WriteOnly ).write( file.data(), file.size() );
+///
+/// The key stays inside this process: it goes to the device as eleven round keys
+/// in a kernel's arguments, never to a file.
+class GpuBundleSealer: NoCopy
+{
+  ZcContextPool pool;
+  bool keyed;
+  uint8_t key[ 16 ];
+
+public:
+  explicit GpuBundleSealer( EncryptionKey const & encryptionKey, int device = 0 ):
+    pool( device ), keyed( encryptionKey.hasKey() )
+  {
+    memset( key, 0, sizeof( key ) );
+    if ( keyed )
+      memcpy( key, encryptionKey.getKey(), sizeof( key ) );
+  }
+
+  bool hasKey() const { return keyed; }
+
+  void seal( string const & prefix, string const & body, string & file )
+  {
+    std::vector< string const * > p( 1, &prefix ), b( 1, &body );
+    std::vector< string > out;
+    sealAll( p, b, out );
+    file.swap( out[ 0 ] );
+  }
+
+  /// several finished bundles in one device call
+  void sealAll( std::vector< string const * > const & prefixes, std::vector< string const * > const & bodies,
+                std::vector< string > & files )
+  {
+    size_t n = prefixes.size();
+    if ( bodies.size() != n )
+      throw std::logic_error( "GpuBundleSealer: prefixes and bodies differ in number" );
+    std::vector< zc_bundle_file > desc( n );
+    std::vector< uint64_t > fileSize( n );
+    string prefixBlob, bodyBlob, out;
+    uint64_t filePos = 0;
+    for ( size_t i = 0; i < n; ++i )
+    {
+      desc[ i ].prefix_off = prefixBlob.size();
+      desc[ i ].prefix_len = prefixes[ i ]->size();
+      desc[ i ].body_off = bodyBlob.size();
+      desc[ i ].body_len = bodies[ i ]->size();
+      desc[ i ].file_off = filePos;
+      prefixBlob += *prefixes[ i ];
+      bodyBlob += *bodies[ i ];
+      uint64_t size = zc_bundle_file_size( desc[ i ].prefix_len, desc[ i ].body_len, keyed );
+      filePos += ( size + 15 ) / 16 * 16;
+    }
+    out.resize( filePos ? filePos : 1 );
+    zc_ctx * ctx = pool.acquire();
+    int rc = zc_bundle_seal_host( ctx, keyed ? key : 0, prefixBlob.data(), desc.data(), n, bodyBlob.data(),
+                                  &out[ 0 ], fileSize.data() );
+    string err = rc == ZC_OK ? string() : string( zc_last_error( ctx ) );
+    pool.release( ctx );
+    if ( rc != ZC_OK )
+      throw std::runtime_error( err );
+    files.resize( n );
+    for ( size_t i = 0; i < n; ++i )
+      files[ i ].assign( out, desc[ i ].file_off, fileSize[ i ] );
+  }
+};
+
+/// The read side, in front of Bundle::Reader (bundle.cc:157-218): the file's
+/// bytes go in (UnbufferedFile::read of the whole file), the two serialized
+/// messages and the compressed body come out, decrypted and with both Adler-32s
+/// and the padding checked on the GPU.  Reader parses the messages from strings
+/// (ArrayInputStream + Message::parse) and feeds `body` to its decoder as before.
+/// A file the reference would refuse throws here, under the name the reference
+/// throws (exIncorrectFileSize, exBadPadding, exAdlerMismatch, or a parse error).
+class GpuBundleUnsealer: NoCopy
+{
+  ZcContextPool pool;
+  bool keyed;
+  uint8_t key[ 16 ];
+
+public:
+  struct Opened
+  {
+    string header, info, body;  // BundleFileHeader and BundleInfo (serialized), the compressed body
+  };
+
+  explicit GpuBundleUnsealer( EncryptionKey const & encryptionKey, int device = 0 ):
+    pool( device ), keyed( encryptionKey.hasKey() )
+  {
+    memset( key, 0, sizeof( key ) );
+    if ( keyed )
+      memcpy( key, encryptionKey.getKey(), sizeof( key ) );
+  }
+
+  static char const * statusName( int status )
+  {
+    switch ( status )
+    {
+      case ZC_BUNDLE_OK: return "ok";
+      case ZC_BUNDLE_BAD_SIZE: return "exIncorrectFileSize";
+      case ZC_BUNDLE_TRUNCATED: return "the file ends inside its header (Message::parse fails)";
+      case ZC_BUNDLE_BAD_ADLER1: return "exAdlerMismatch after BundleInfo";
+      case ZC_BUNDLE_BAD_ADLER2: return "exAdlerMismatch after the payload";
+      case ZC_BUNDLE_BAD_PADDING: return "exBadPadding";
+      default: return "unknown status";
+    }
+  }
+
+  void unseal( string const & file, Opened & opened )
+  {
+    std::vector< string const * > f( 1, &file );
+    std::vector< Opened > out;
+    std::vector< int > status;
+    unsealAll( f, out, status );
+    if ( status[ 0 ] != ZC_BUNDLE_OK )
+      throw std::runtime_error( string( "bundle file: " ) + statusName( status[ 0 ] ) );
+    opened.header.swap( out[ 0 ].header );
+    opened.info.swap( out[ 0 ].info );
+    opened.body.swap( out[ 0 ].body );
+  }
+
+  /// several files in one device call (a restore knows the bundles it needs
+  /// up front); status[ i ] != ZC_BUNDLE_OK leaves opened[ i ] empty
+  void unsealAll( std::vector< string const * > const & files, std::vector< Opened > & opened,
+                  std::vector< int > & status )
+  {
+    size_t n = files.size();
+    std::vector< uint64_t > off( n ), size( n );
+    std::vector< zc_bundle_layout > layout( n );
+    string in, plain;
+    for ( size_t i = 0; i < n; ++i )
+    {
+      off[ i ] = in.size();
+      size[ i ] = files[ i ]->size();
+      in += *files[ i ];
+      in.resize( ( in.size() + 15 ) / 16 * 16 );  // every file at a 16-byte offset
+    }
+    if ( in.empty() )
+      in.resize( 16 );
+    plain.resize( in.size() );
+    zc_ctx * ctx = pool.acquire();
+    int rc = zc_bundle_unseal_host( ctx, keyed ? key : 0, in.data(), off.data(), size.data(), n, &plain[ 0 ],
+                                    off.data(), layout.data() );
+    string err = rc == ZC_OK ? string() : string( zc_last_error( ctx ) );
+    pool.release( ctx );
+    if ( rc != ZC_OK )
+      throw std::runtime_error( err );
+    opened.assign( n, Opened() );
+    status.resize( n );
+    for ( size_t i = 0; i < n; ++i )
+    {
+      status[ i ] = layout[ i ].status;
+      if ( status[ i ] != ZC_BUNDLE_OK )
+        continue;
+      opened[ i ].header.assign( plain, off[ i ] + layout[ i ].header_off, layout[ i ].header_len );
+      opened[ i ].info.assign( plain, off[ i ] + layout[ i ].info_off, layout[ i ].info_len );
+      opened[ i ].body.assign( plain, off[ i ] + layout[ i ].body_off, layout[ i ].body_len );
+    }
   }
 };
 

@@ -21,7 +21,14 @@ EXPORTS = ["zc_create", "zc_destroy", "zc_seed_index", "zc_get_input_buffer",
            "zc_forget_stream_chunks", "zc_set_window", "zc_get_window", "zc_take_records", "zc_sha256_create", "zc_sha256_add", "zc_sha256_finish", "zc_sha256_destroy", "zc_sha256_impl",
            "zc_bundle_plan", "zc_bundle_gather", "zc_lzo_capacity", "zc_lzo_compress", "zc_lzo_compress_host", "zc_lzo_last_stats", "zc_adler32", "zc_serialize_records", "zc_stream_data", "zc_build_id",
            "zc_seed_index_meta", "zc_export_chunk_meta", "zc_anchor_def",
-           "zc_lzo_frame_info", "zc_bundle_scatter", "zc_parse_instructions"]
+           "zc_lzo_frame_info", "zc_bundle_scatter", "zc_parse_instructions",
+           "zc_aes128_cbc_encrypt", "zc_aes128_cbc_decrypt", "zc_aes128_cbc_encrypt_host",
+           "zc_aes128_cbc_decrypt_host", "zc_bundle_file_size", "zc_bundle_seal", "zc_bundle_seal_host",
+           "zc_bundle_unseal", "zc_bundle_unseal_host"]
+ZC_BUNDLE_OK, ZC_BUNDLE_BAD_SIZE, ZC_BUNDLE_TRUNCATED = 0, 1, 2
+ZC_BUNDLE_BAD_ADLER1, ZC_BUNDLE_BAD_ADLER2, ZC_BUNDLE_BAD_PADDING = 3, 4, 5
+BUNDLE_STATUS_NAMES = {0: "ok", 1: "bad file size", 2: "truncated", 3: "Adler-32 mismatch after BundleInfo",
+                       4: "Adler-32 mismatch after the body", 5: "bad padding"}
 ZC_LZO_E_FRAME, ZC_LZO_E_SIZE = -100, -101
 ZC_INSTR_CHUNK, ZC_INSTR_BYTES = 0, 1
 ZC_META_NO_ANCHOR = 0xFFFFFFFF
@@ -46,6 +53,17 @@ class ZcChunkMeta(ctypes.Structure):
 class ZcInstruction(ctypes.Structure):
     _fields_ = [("kind", ctypes.c_uint32), ("id", ctypes.c_uint8 * 24), ("reserved", ctypes.c_uint32),
                 ("data_off", ctypes.c_uint64), ("size", ctypes.c_uint64)]
+
+
+class ZcBundleFile(ctypes.Structure):
+    _fields_ = [("prefix_off", ctypes.c_uint64), ("prefix_len", ctypes.c_uint64), ("body_off", ctypes.c_uint64),
+                ("body_len", ctypes.c_uint64), ("file_off", ctypes.c_uint64)]
+
+
+class ZcBundleLayout(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_int32), ("reserved", ctypes.c_uint32), ("header_off", ctypes.c_uint64),
+                ("header_len", ctypes.c_uint64), ("info_off", ctypes.c_uint64), ("info_len", ctypes.c_uint64),
+                ("body_off", ctypes.c_uint64), ("body_len", ctypes.c_uint64)]
 
 
 class ZcStats(ctypes.Structure):
@@ -132,6 +150,18 @@ def load(path=LIB_PATH):
         "zc_lzo_frame_info": (i32, [vp, sz, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
         "zc_bundle_scatter": (i32, [vp, vp, vp, vp, sz, vp, vp]),
         "zc_parse_instructions": (i32, [vp, sz, vp, sz, ctypes.POINTER(sz)]),
+        # encrypted repositories: (ctx, key, in, in_off, len, n, iv, out, out_off)
+        "zc_aes128_cbc_encrypt": (i32, [vp, vp, vp, vp, vp, sz, vp, vp, vp]),
+        "zc_aes128_cbc_decrypt": (i32, [vp, vp, vp, vp, vp, sz, vp, vp, vp]),
+        "zc_aes128_cbc_encrypt_host": (i32, [vp, vp, vp, vp, vp, sz, vp, vp, vp]),
+        "zc_aes128_cbc_decrypt_host": (i32, [vp, vp, vp, vp, vp, sz, vp, vp, vp]),
+        "zc_bundle_file_size": (u64, [u64, u64, i32]),
+        # (ctx, key, prefix, files, n, body, files_out, file_size)
+        "zc_bundle_seal": (i32, [vp, vp, vp, vp, sz, vp, vp, vp]),
+        "zc_bundle_seal_host": (i32, [vp, vp, vp, vp, sz, vp, vp, vp]),
+        # (ctx, key, files, file_off, file_size, n, plain, plain_off, layout)
+        "zc_bundle_unseal": (i32, [vp, vp, vp, vp, vp, sz, vp, vp, vp]),
+        "zc_bundle_unseal_host": (i32, [vp, vp, vp, vp, vp, sz, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

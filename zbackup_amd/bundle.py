@@ -10,6 +10,11 @@ chunk a restore emits (bundle.cc:235-251), `parse_backup_data` the instruction
 parse of restore() (backup_restorer.cc:38-107), `frame_info` the frame a
 bundle's lzo1x stream is stored under (compression.cc:369-402).
 
+For encrypted repositories: `BundleCompressor.seal` / `.unseal` are the bundle
+file EncryptedFile::OutputStream writes and InputStream reads back
+(encrypted_file.cc:20-392, bundle.cc:96-218), `aes_encrypt` / `aes_decrypt`
+the AES-128-CBC under them (encryption.cc:17-95).
+
 `plan_bundles` is host bookkeeping; `BundleCompressor.gather` and `.compress`
 run on the GPU through libzchunk.so (zc_bundle_gather / zc_lzo_compress);
 there is no CPU fallback.  Device buffers are passed as raw pointers (e.g. a
@@ -44,6 +49,50 @@ def plan_bundles(sizes, max_payload=MAX_PAYLOAD_SIZE):
 def lzo_capacity(payload_size):
     """Output bytes to reserve for one framed payload (suggestOutputSize + 16)."""
     return int(_lib.load().zc_lzo_capacity(int(payload_size)))
+
+
+LAYOUT_DTYPE = np.dtype([("status", "<i4"), ("reserved", "<u4"), ("header_off", "<u8"), ("header_len", "<u8"),
+                         ("info_off", "<u8"), ("info_len", "<u8"), ("body_off", "<u8"), ("body_len", "<u8")])
+assert LAYOUT_DTYPE.itemsize == ctypes.sizeof(_lib.ZcBundleLayout)
+
+
+def bundle_file_size(prefix_len, body_len, keyed):
+    """Bytes of a bundle file whose prefix (R + both messages) and body have
+    these lengths (zc_bundle_file_size; host arithmetic)."""
+    return int(_lib.load().zc_bundle_file_size(int(prefix_len), int(body_len), 1 if keyed else 0))
+
+
+def _key16(key, none_ok=False):
+    if key is None and none_ok:
+        return None
+    key = bytes(key) if key is not None else None
+    if key is not None and len(key) != 16:
+        raise ValueError("an AES-128 key is 16 bytes (EncryptionKey::getKey)")
+    return key
+
+
+def _bundle_files(prefixes, body_off, body_len, file_off):
+    """(zc_bundle_file array, the prefixes' blob) of a seal call."""
+    prefixes = [bytes(p) for p in prefixes]
+    if not len(prefixes) == len(body_off) == len(body_len) == len(file_off):
+        raise ValueError("seal: prefixes, body_off, body_len and file_off differ in length")
+    files = (_lib.ZcBundleFile * max(len(prefixes), 1))()
+    pos = 0
+    for k, p in enumerate(prefixes):
+        files[k] = _lib.ZcBundleFile(pos, len(p), int(body_off[k]), int(body_len[k]), int(file_off[k]))
+        pos += len(p)
+    return _Counted(files, len(prefixes)), b"".join(prefixes) or b"\0"
+
+
+class _Counted:
+    """A ctypes array passed by pointer with its element count as len()."""
+
+    def __init__(self, arr, n):
+        self._as_parameter_ = ctypes.cast(arr, ctypes.c_void_p)
+        self._arr, self._n = arr, n
+
+    def __len__(self):
+        return self._n
 
 
 class BundleCompressor:
@@ -105,6 +154,109 @@ class BundleCompressor:
         out = np.zeros(len(off), dtype=np.uint32)
         rc = self._L.zc_adler32(self._ctx, d_base, off.ctypes.data, length.ctypes.data, len(off), out.ctypes.data)
         _check(self._L, self._ctx, rc, "zc_adler32")
+        return out
+
+    # ---- encrypted repositories (encryption.cc:17-95, encrypted_file.cc:239-392) ----
+
+    def _aes(self, fn, what, key, src, in_off, length, iv, dst, out_off):
+        in_off, length, out_off = _u64(in_off), _u64(length), _u64(out_off)
+        if not len(in_off) == len(length) == len(out_off):
+            raise ValueError(f"{what}: in_off, length and out_off differ in length")
+        key = _key16(key)
+        if iv is not None:
+            iv = bytes(iv)
+            if len(iv) != 16 * len(length):
+                raise ValueError(f"{what}: iv must hold 16 bytes per chain")
+        rc = fn(self._ctx, key, src, in_off.ctypes.data, length.ctypes.data, len(length), iv, dst, out_off.ctypes.data)
+        _check(self._L, self._ctx, rc, what)
+
+    def aes_encrypt(self, key, d_in, in_off, length, d_out, out_off, iv=None):
+        """AES-128-CBC of chain i, d_in[in_off[i] ..+ length[i]), to d_out +
+        out_off[i]; iv = 16 bytes per chain, None: the zero IV.  A chain may be
+        encrypted in place (the same extent in and out)."""
+        self._aes(self._L.zc_aes128_cbc_encrypt, "zc_aes128_cbc_encrypt", key, d_in, in_off, length, iv, d_out,
+                  out_off)
+
+    def aes_decrypt(self, key, d_in, in_off, length, d_out, out_off, iv=None):
+        """The inverse, out of place only (no input extent may touch an output extent)."""
+        self._aes(self._L.zc_aes128_cbc_decrypt, "zc_aes128_cbc_decrypt", key, d_in, in_off, length, iv, d_out,
+                  out_off)
+
+    def seal(self, key, prefixes, d_body, body_off, body_len, d_files, file_off):
+        """Bundle::Creator::write's file for every bundle: prefixes[i] (host
+        bytes: the 16 random bytes R when keyed, then the serialized
+        BundleFileHeader and BundleInfo messages), the Adler-32s, the body
+        d_body[body_off[i] ..+ body_len[i]) and the padding, assembled at
+        d_files + file_off[i] and encrypted there (key None: no R, no padding,
+        no cipher).  Returns the files' sizes."""
+        files, blob = _bundle_files(prefixes, body_off, body_len, file_off)
+        size = np.zeros(len(files), dtype=np.uint64)
+        rc = self._L.zc_bundle_seal(self._ctx, _key16(key, none_ok=True), blob, files, len(files), d_body, d_files,
+                                    size.ctypes.data)
+        _check(self._L, self._ctx, rc, "zc_bundle_seal")
+        return size
+
+    def seal_host(self, key, prefixes, bodies):
+        """Host bytes in, each bundle's file bytes out (zc_bundle_seal_host), one call for all."""
+        bodies = [bytes(b) for b in bodies]
+        blen = [len(b) for b in bodies]
+        boff = np.concatenate([[0], np.cumsum(blen)[:-1]]) if blen else []
+        sizes = [bundle_file_size(len(p), n, key is not None) for p, n in zip(prefixes, blen)]
+        cap = [(s + 15) // 16 * 16 for s in sizes]
+        foff = np.concatenate([[0], np.cumsum(cap)[:-1]]) if cap else []
+        files, blob = _bundle_files(prefixes, boff, blen, foff)
+        body = np.frombuffer(b"".join(bodies) or b"\0", dtype=np.uint8)
+        out = np.zeros(int(sum(cap)) or 1, dtype=np.uint8)
+        size = np.zeros(len(files), dtype=np.uint64)
+        rc = self._L.zc_bundle_seal_host(self._ctx, _key16(key, none_ok=True), blob, files, len(files),
+                                         body.ctypes.data, out.ctypes.data, size.ctypes.data)
+        _check(self._L, self._ctx, rc, "zc_bundle_seal_host")
+        assert [int(s) for s in size] == sizes
+        return [out[int(o):int(o) + int(s)].tobytes() for o, s in zip(foff, size)]
+
+    def unseal(self, key, d_files, file_off, file_size, d_plain, plain_off):
+        """Bundle::Reader's side: file i, d_files[file_off[i] ..+ file_size[i]),
+        decrypted to d_plain + plain_off[i] and checked.  Returns a
+        LAYOUT_DTYPE array: per bundle its status (ZC_BUNDLE_*) and where the
+        header message, the info message and the body lie in its plaintext."""
+        file_off, file_size, plain_off = _u64(file_off), _u64(file_size), _u64(plain_off)
+        layout = np.zeros(len(file_off), dtype=LAYOUT_DTYPE)
+        rc = self._L.zc_bundle_unseal(self._ctx, _key16(key, none_ok=True), d_files, file_off.ctypes.data,
+                                      file_size.ctypes.data, len(file_off), d_plain, plain_off.ctypes.data,
+                                      layout.ctypes.data)
+        _check(self._L, self._ctx, rc, "zc_bundle_unseal")
+        return layout
+
+    def unseal_host(self, key, files, strict=True):
+        """Bundle files (host bytes) to (header bytes, info bytes, body bytes)
+        each: what a caller hands to its protobuf decoder, to liblzo2 and then
+        to the Restorer.  A file the reference would refuse raises ZcError
+        with its status (strict=False: its entry is the status instead)."""
+        files = [bytes(f) for f in files]
+        size = np.array([len(f) for f in files], dtype=np.uint64)
+        cap = (size + np.uint64(15)) // np.uint64(16) * np.uint64(16)
+        off = np.concatenate([[0], np.cumsum(cap)[:-1]]).astype(np.uint64) if len(files) else size
+        src = np.zeros(int(cap.sum()) or 1, dtype=np.uint8)
+        for o, f in zip(off, files):
+            src[int(o):int(o) + len(f)] = np.frombuffer(f, dtype=np.uint8)
+        plain = np.zeros(len(src), dtype=np.uint8)
+        layout = np.zeros(len(files), dtype=LAYOUT_DTYPE)
+        rc = self._L.zc_bundle_unseal_host(self._ctx, _key16(key, none_ok=True), src.ctypes.data, off.ctypes.data,
+                                           size.ctypes.data, len(files), plain.ctypes.data, off.ctypes.data,
+                                           layout.ctypes.data)
+        _check(self._L, self._ctx, rc, "zc_bundle_unseal_host")
+        out = []
+        for k, (o, lay) in enumerate(zip(off, layout)):
+            st = int(lay["status"])
+            if st != _lib.ZC_BUNDLE_OK:
+                if strict:
+                    raise _lib.ZcError(f"bundle file {k}: {_lib.BUNDLE_STATUS_NAMES.get(st, st)} (status {st})")
+                out.append(st)
+                continue
+            p = plain[int(o):int(o) + int(size[k])]
+            out.append(tuple(p[int(lay[a]):int(lay[a]) + int(lay[b])].tobytes()
+                             for a, b in (("header_off", "header_len"), ("info_off", "info_len"),
+                                          ("body_off", "body_len"))))
         return out
 
     def last_stats(self):

@@ -6,6 +6,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <string>
+
+struct zc_bundle_file;    // include/zchunk.h
+struct zc_bundle_layout;
+
 namespace zc {
 
 // Stream geometry.  One lane owns a contiguous span of ZC_SPAN bytes; the
@@ -494,5 +499,23 @@ hipError_t lzo_compress(LzoScratch* s, const uint8_t* d_payload, const uint64_t*
 // restore: d_dst + dst_off[i] <- d_src[off[i] ..+ size[i]), the inverse of lzo_gather
 hipError_t lzo_scatter(LzoScratch* s, const uint8_t* d_src, const uint64_t* off, const uint64_t* size, size_t n,
                        uint8_t* d_dst, const uint64_t* dst_off, hipStream_t st);
+
+// zc_aes.hip: AES-128-CBC chains and the bundle file around them (zc_aes_core.h).
+// Each returns a zc_status; on failure `err` holds the message.  Arguments are
+// validated before any device work; ev_in (if given) then orders the context
+// stream after the legacy default stream, as the other bundle calls do.
+struct AesScratch;
+AesScratch* aes_scratch_new();
+void aes_scratch_free(AesScratch* s);
+int aes_cbc(AesScratch* s, bool decrypt, bool host, const uint8_t* key, const void* in, const uint64_t* in_off,
+            const uint64_t* len, size_t n, const uint8_t* iv, void* out, const uint64_t* out_off, hipEvent_t ev_in,
+            hipStream_t st, std::string& err);
+int bundle_seal(AesScratch* s, LzoScratch* lz, bool host, const uint8_t* key, const void* prefix,
+                const zc_bundle_file* files, size_t n, const void* body, void* files_out, uint64_t* file_size,
+                hipEvent_t ev_in, hipStream_t st, std::string& err);
+int bundle_unseal(AesScratch* s, LzoScratch* lz, bool host, const uint8_t* key, const void* files,
+                  const uint64_t* file_off, const uint64_t* file_size, size_t n, void* plain,
+                  const uint64_t* plain_off, zc_bundle_layout* layout, hipEvent_t ev_in, hipStream_t st,
+                  std::string& err);
 
 }  // namespace zc

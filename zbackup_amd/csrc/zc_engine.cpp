@@ -521,6 +521,7 @@ struct zc_ctx {
 
   LzoScratch* lzo = nullptr;  // bundle compression (zc_lzo.hip), made on first use
   DevBuf<uint8_t> lzo_in, lzo_out;  // zc_lzo_compress_host's device copies
+  AesScratch* aes = nullptr;  // AES-128-CBC and bundle files (zc_aes.hip), made on first use
 
   // scratch
   DevBuf<uint64_t> hm_key, hm_fp, hm_rkey;  // metadata of chunks joining the historic index
@@ -3300,6 +3301,7 @@ int zc_destroy(zc_ctx* c) {
     if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     lzo_scratch_free(c->lzo);
+    aes_scratch_free(c->aes);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     if (prev >= 0) (void)hipSetDevice(prev);
@@ -4047,4 +4049,106 @@ int zc_parse_instructions(const void* data, size_t n, zc_instruction* out, size_
   }
   g_host_err.clear();
   return ZC_OK;
+}
+
+// ---- encrypted repositories: AES-128-CBC chains and the bundle file (zc_aes.hip) ----
+
+// the common frame of the calls below: f(err) validates its arguments before any
+// device work and returns a zc_status with its message in err
+template <class F>
+static int aes_entry(zc_ctx* c, const char* what, F&& f) {
+  if (!c) return ctx_arg_error(c, (std::string(what) + ": null context").c_str());
+  std::string err;
+  int rc;
+  try {
+    DeviceGuard g(c->device);
+    if (!c->aes) c->aes = aes_scratch_new();
+    if (!c->lzo) c->lzo = lzo_scratch_new();
+    rc = f(err);
+  } catch (const ZcError& e) {
+    return fail(c, e);
+  } catch (const std::bad_alloc&) {
+    return fail(c, ZcError{ZC_ERR_NOMEM, "host allocation failed"});
+  }
+  if (rc != ZC_OK)
+    c->err = std::string(what) + ": " + err;
+  else
+    c->err.clear();
+  return rc;
+}
+
+int zc_aes128_cbc_encrypt(zc_ctx* c, const uint8_t key[16], const void* d_in, const uint64_t* in_off,
+                          const uint64_t* len, size_t n, const uint8_t* iv, void* d_out, const uint64_t* out_off) {
+  ZC_LOCK(c);
+  return aes_entry(c, "zc_aes128_cbc_encrypt", [&](std::string& err) {
+    return aes_cbc(c->aes, false, false, key, d_in, in_off, len, n, iv, d_out, out_off, c->ev_in, c->stream, err);
+  });
+}
+
+int zc_aes128_cbc_decrypt(zc_ctx* c, const uint8_t key[16], const void* d_in, const uint64_t* in_off,
+                          const uint64_t* len, size_t n, const uint8_t* iv, void* d_out, const uint64_t* out_off) {
+  ZC_LOCK(c);
+  return aes_entry(c, "zc_aes128_cbc_decrypt", [&](std::string& err) {
+    return aes_cbc(c->aes, true, false, key, d_in, in_off, len, n, iv, d_out, out_off, c->ev_in, c->stream, err);
+  });
+}
+
+int zc_aes128_cbc_encrypt_host(zc_ctx* c, const uint8_t key[16], const void* in, const uint64_t* in_off,
+                               const uint64_t* len, size_t n, const uint8_t* iv, void* out,
+                               const uint64_t* out_off) {
+  ZC_LOCK(c);
+  return aes_entry(c, "zc_aes128_cbc_encrypt_host", [&](std::string& err) {
+    return aes_cbc(c->aes, false, true, key, in, in_off, len, n, iv, out, out_off, nullptr, c->stream, err);
+  });
+}
+
+int zc_aes128_cbc_decrypt_host(zc_ctx* c, const uint8_t key[16], const void* in, const uint64_t* in_off,
+                               const uint64_t* len, size_t n, const uint8_t* iv, void* out,
+                               const uint64_t* out_off) {
+  ZC_LOCK(c);
+  return aes_entry(c, "zc_aes128_cbc_decrypt_host", [&](std::string& err) {
+    return aes_cbc(c->aes, true, true, key, in, in_off, len, n, iv, out, out_off, nullptr, c->stream, err);
+  });
+}
+
+uint64_t zc_bundle_file_size(uint64_t prefix_len, uint64_t body_len, int keyed) {
+  return keyed ? (prefix_len + 4 + body_len + 4) / 16 * 16 + 16 : prefix_len + body_len + 8;
+}
+
+int zc_bundle_seal(zc_ctx* c, const uint8_t* key, const void* prefix, const zc_bundle_file* files, size_t n,
+                   const void* d_body, void* d_files, uint64_t* file_size) {
+  ZC_LOCK(c);
+  return aes_entry(c, "zc_bundle_seal", [&](std::string& err) {
+    return bundle_seal(c->aes, c->lzo, false, key, prefix, files, n, d_body, d_files, file_size, c->ev_in, c->stream,
+                       err);
+  });
+}
+
+int zc_bundle_seal_host(zc_ctx* c, const uint8_t* key, const void* prefix, const zc_bundle_file* files, size_t n,
+                        const void* body, void* files_out, uint64_t* file_size) {
+  ZC_LOCK(c);
+  return aes_entry(c, "zc_bundle_seal_host", [&](std::string& err) {
+    return bundle_seal(c->aes, c->lzo, true, key, prefix, files, n, body, files_out, file_size, nullptr, c->stream,
+                       err);
+  });
+}
+
+int zc_bundle_unseal(zc_ctx* c, const uint8_t* key, const void* d_files, const uint64_t* file_off,
+                     const uint64_t* file_size, size_t n, void* d_plain, const uint64_t* plain_off,
+                     zc_bundle_layout* layout) {
+  ZC_LOCK(c);
+  return aes_entry(c, "zc_bundle_unseal", [&](std::string& err) {
+    return bundle_unseal(c->aes, c->lzo, false, key, d_files, file_off, file_size, n, d_plain, plain_off, layout,
+                         c->ev_in, c->stream, err);
+  });
+}
+
+int zc_bundle_unseal_host(zc_ctx* c, const uint8_t* key, const void* files, const uint64_t* file_off,
+                          const uint64_t* file_size, size_t n, void* plain, const uint64_t* plain_off,
+                          zc_bundle_layout* layout) {
+  ZC_LOCK(c);
+  return aes_entry(c, "zc_bundle_unseal_host", [&](std::string& err) {
+    return bundle_unseal(c->aes, c->lzo, true, key, files, file_off, file_size, n, plain, plain_off, layout, nullptr,
+                         c->stream, err);
+  });
 }
