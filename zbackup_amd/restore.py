@@ -12,7 +12,8 @@ call, HBM to HBM.  Decoding the referenced bundles' lzo1x streams into the
 scratch buffer is the caller's step between the two (liblzo2's
 lzo1x_decompress_safe, as the reference calls it, compression.cc:472-490;
 `bundle.frame_info` reads the frame): the instruction stream travels to the
-device in the same buffer, so there is one upload.
+device in the same buffer, so there is one upload (`RestorePlan.host_image`;
+`RestorePlan.instruction_image` is the instruction stream's share of it alone).
 """
 import numpy as np
 
@@ -60,6 +61,15 @@ class RestorePlan:
             img[self.pay_off[k]:self.pay_off[k] + len(p)] = np.frombuffer(bytes(p), dtype=np.uint8)
         img[self.instr_off:self.instr_off + len(self.data)] = np.frombuffer(self.data, dtype=np.uint8)
         return img
+
+
+    def instruction_image(self):
+        """(offset in the scratch buffer, the bytes that belong there): the
+        instruction stream alone, whose bytes_to_emit runs the scatter list
+        reads.  All of the scratch buffer that has to come from the host when
+        the payloads are put at pay_off[k] on the device; host_image() is
+        this plus the payloads."""
+        return self.instr_off, np.frombuffer(self.data, dtype=np.uint8)
 
 
 class Restorer:
