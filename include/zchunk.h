@@ -370,6 +370,20 @@ int zc_aes128_cbc_decrypt_host(zc_ctx* ctx, const uint8_t key[16], const void* i
                                const uint64_t* len, size_t n, const uint8_t* iv, void* out,
                                const uint64_t* out_off);
 
+/* Which CBC kernel the context's last launch dispatched (a chain call, or a seal / unseal with a
+ * key).  The library compiles several forms of each kernel and picks one per call from the
+ * environment (ZC_AES_TABLE=shared, ZC_AES_ENC=lane, ZC_AES_CPW=<1..64>, ZC_AES_PREFETCH=1: kept
+ * for measurements); this reports the one that ran, recorded where it is launched.
+ * ZC_ERR_ARG with a message when the context has launched no CBC kernel yet. */
+enum {
+  ZC_AES_FORM_DECRYPT = 1,       /* the decrypt kernel */
+  ZC_AES_FORM_PLAIN_TABLES = 2,  /* plain 1 KiB tables in LDS, not the 32-fold replicated ones */
+  ZC_AES_FORM_LANE = 4,          /* the lane-per-chain encrypt kernel, not four lanes per chain */
+  ZC_AES_FORM_AHEAD_1 = 8,       /* the lane kernel reads one block ahead, not four */
+  ZC_AES_FORM_CPW_SHIFT = 8      /* bits 8-15: chains per wave of the lane kernel, else 0 */
+};
+int zc_aes_last_form(const zc_ctx* ctx, uint32_t* form);
+
 /* A bundle file's plaintext: [R: 16 random bytes, with a key only] BundleFileHeader message,
  * BundleInfo message (each a varint32 length + that many bytes, message.cc:16-22), A1, the
  * compressed body (zc_lzo_compress's framed bytes), A2 [, PKCS#7 padding of 1..16 bytes with a

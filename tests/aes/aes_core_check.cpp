@@ -3,7 +3,8 @@
 // AES_encrypt / AES_decrypt on the FIPS-197 C.1 and SP 800-38A F.2.1 / F.2.2
 // vectors and on random key / block pairs; a host CBC loop over the core
 // against the library's CBC at 1, 2, 3 and 4,097 blocks; the Adler-32 helpers
-// and the plaintext parser's arithmetic.  Prints "ok <checks>"; exits non-zero
+// and the plaintext parser: no read past the end on random bytes, and exact
+// fields for well-formed plaintexts at every pair of varint widths.  Prints "ok <checks>"; exits non-zero
 // on the first difference.
 #include <openssl/aes.h>
 #include <stdint.h>
@@ -58,6 +59,33 @@ struct Bytes {
   const uint8_t* p;
   uint32_t byte(uint64_t i) const { return p[i]; }
 };
+
+// v as a varint of exactly `width` bytes: above the canonical width the last
+// canonical byte gets a continuation bit and 0x80 bytes follow, up to a final 0
+static void put_varint(std::vector<uint8_t>& d, uint64_t v, int width) {
+  int n = 0;
+  do {
+    d.push_back((uint8_t)((v & 0x7f) | (v >> 7 || n + 1 < width ? 0x80 : 0)));
+    v >>= 7;
+    ++n;
+  } while (v || n < width);
+  if (n != width) die("put_varint width", width);
+}
+static void put_le32(std::vector<uint8_t>& d, uint32_t v) {
+  for (int k = 0; k < 4; ++k) d.push_back((uint8_t)(v >> (8 * k)));
+}
+// what a reader makes of a plaintext: parse_plain, then both Adler-32s as
+// zc_bundle_unseal checks them (the share before A1, joined with the share
+// from A1 to A2)
+static int reader_status(const std::vector<uint8_t>& d, bool keyed, zcaes::Parsed* p) {
+  zcaes::parse_plain(Bytes{d.data()}, d.size(), keyed, p);
+  if (p->status != zcaes::kBundleOk) return p->status;
+  const uint32_t a1 = zcaes::adler32_host(d.data(), p->a1_off);
+  if (a1 != p->a1) return zcaes::kBundleAdler1;
+  const uint64_t n2 = 4 + p->body_len;
+  if (zcaes::adler32_join(a1, zcaes::adler32_host(d.data() + p->a1_off, n2), n2) != p->a2) return zcaes::kBundleAdler2;
+  return zcaes::kBundleOk;
+}
 
 int main() {
   zcaes::make_tables(&T);
@@ -177,6 +205,48 @@ int main() {
     }
     ++checks;
   }
+  // well-formed plaintexts, built here: both length varints at every width 1..5
+  // (padded with 0x80 continuation bytes above the canonical width) x three
+  // (header, info, body) length triples, keyed and plain; every field exact.
+  // The same plaintext cut by one keyed block, or by one byte when plain, must
+  // not read as a good file.
+  for (int keyed = 0; keyed < 2; ++keyed)
+    for (int tr = 0; tr < 3; ++tr)
+      for (int wh = 1; wh <= 5; ++wh)
+        for (int wi = 1; wi <= 5; ++wi) {
+          static const uint64_t kTriples[3][3] = {{0, 0, 0}, {2, 5, 1}, {3, 127, 33}};
+          const uint64_t H = kTriples[tr][0], I = kTriples[tr][1], B = kTriples[tr][2];
+          const long id = ((keyed * 3 + tr) * 5 + (wh - 1)) * 5 + (wi - 1);
+          std::vector<uint8_t> d;
+          auto put_random = [&](uint64_t n) {
+            for (uint64_t k = 0; k < n; ++k) d.push_back((uint8_t)rnd());
+          };
+          if (keyed) put_random(16);  // R
+          const uint64_t start = d.size();
+          put_varint(d, H, wh);
+          put_random(H);
+          put_varint(d, I, wi);
+          put_random(I);
+          const uint32_t a1 = zcaes::adler32_host(d.data(), d.size());
+          put_le32(d, a1);
+          put_random(B);
+          const uint32_t a2 = zcaes::adler32_host(d.data(), d.size());
+          put_le32(d, a2);
+          const uint32_t pad = keyed ? 16 - (uint32_t)(d.size() % 16) : 0;
+          d.insert(d.end(), pad, (uint8_t)pad);
+          if (d.size() != zcaes::bundle_file_size(start + wh + H + wi + I, B, keyed != 0)) die("well-formed size", id);
+          zcaes::Parsed p;
+          if (reader_status(d, keyed != 0, &p) != zcaes::kBundleOk) die("well-formed status", id);
+          if (p.header_off != start + wh || p.header_len != H) die("well-formed header", id);
+          if (p.info_off != start + wh + H + wi || p.info_len != I) die("well-formed info", id);
+          if (p.a1_off != p.info_off + I || p.body_off != p.a1_off + 4 || p.body_len != B) die("well-formed body", id);
+          if (p.pad != pad || p.a1 != a1 || p.a2 != a2) die("well-formed pad / A1 / A2", id);
+          if (p.body_off + B + 4 + pad != d.size()) die("well-formed end", id);
+          ++checks;
+          const std::vector<uint8_t> cut(d.begin(), d.end() - (keyed ? 16 : 1));  // exactly the bytes left
+          if (reader_status(cut, keyed != 0, &p) == zcaes::kBundleOk) die("cut file reads as good", id);
+          ++checks;
+        }
   if (zcaes::bundle_file_size(20, 4, true) != 48 || zcaes::bundle_file_size(20, 3, true) != 32 ||
       zcaes::bundle_file_size(20, 3, false) != 31)
     die("bundle_file_size", 0);

@@ -4,7 +4,9 @@
   kernels run -- compiled for the host (under ASan + UBSan where that links)
   with a main of its own and compared with libcrypto's AES_encrypt /
   AES_decrypt on the FIPS-197 and SP 800-38A vectors, 10,000 random key /
-  block pairs and CBC chains of 1, 2, 3 and 4,097 blocks;
+  block pairs and CBC chains of 1, 2, 3 and 4,097 blocks; the plaintext
+  parser on random bytes and, with exact fields, on well-formed plaintexts at
+  every pair of varint widths;
 * the reference helper's own checks (tests/aes_ref.py runs them on import);
 * zc_bundle_file_size at every padding residue, and the new symbols."""
 import os
@@ -22,7 +24,7 @@ SSL_INC = next((d for d in ("/usr/include", "/opt/conda/include") if os.path.exi
 
 NEW_SYMBOLS = ["zc_aes128_cbc_encrypt", "zc_aes128_cbc_decrypt", "zc_aes128_cbc_encrypt_host",
                "zc_aes128_cbc_decrypt_host", "zc_bundle_file_size", "zc_bundle_seal", "zc_bundle_seal_host",
-               "zc_bundle_unseal", "zc_bundle_unseal_host"]
+               "zc_bundle_unseal", "zc_bundle_unseal_host", "zc_aes_last_form"]
 
 
 @pytest.fixture(scope="module")
@@ -53,7 +55,8 @@ def test_cipher_core_matches_libcrypto(tmp_path):
     out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stdout + out.stderr[-4000:]
     print(out.stdout, "sanitized" if sanitized else "NOT sanitized")
-    assert int(re.search(r"^ok (\d+)$", out.stdout, re.M).group(1)) >= 20000 + 10
+    # the cipher and Adler-32 checks, 20,000 random plaintexts, 2 x 150 well-formed ones
+    assert int(re.search(r"^ok (\d+)$", out.stdout, re.M).group(1)) >= 20000 + 218 + 20000 + 300
 
 
 def test_reference_helper():
@@ -108,6 +111,19 @@ def test_symbols_are_exported(lib):
     assert lib.zc_abi_version() == 5  # detected by symbol, not by version
     for name in NEW_SYMBOLS:
         assert getattr(lib, name).argtypes is not None
+
+
+def test_last_form_without_a_context(lib):
+    import ctypes
+    form = ctypes.c_uint32(7)
+    assert lib.zc_aes_last_form(None, ctypes.byref(form)) == _lib.ZC_ERR_ARG
+    assert b"zc_aes_last_form" in lib.zc_last_error(None) and form.value == 7
+    assert (_lib.ZC_AES_FORM_DECRYPT, _lib.ZC_AES_FORM_PLAIN_TABLES, _lib.ZC_AES_FORM_LANE, _lib.ZC_AES_FORM_AHEAD_1,
+            _lib.ZC_AES_FORM_CPW_SHIFT) == (1, 2, 4, 8, 8)
+    header = open(os.path.join(ROOT, "include", "zchunk.h")).read()
+    for name in ("DECRYPT", "PLAIN_TABLES", "LANE", "AHEAD_1", "CPW_SHIFT"):
+        value = re.search(r"\bZC_AES_FORM_%s = (\d+)" % name, header).group(1)
+        assert int(value) == getattr(_lib, "ZC_AES_FORM_" + name)
 
 
 def test_null_context_is_an_argument_error_with_a_message(lib):

@@ -24,7 +24,9 @@ EXPORTS = ["zc_create", "zc_destroy", "zc_seed_index", "zc_get_input_buffer",
            "zc_lzo_frame_info", "zc_bundle_scatter", "zc_parse_instructions",
            "zc_aes128_cbc_encrypt", "zc_aes128_cbc_decrypt", "zc_aes128_cbc_encrypt_host",
            "zc_aes128_cbc_decrypt_host", "zc_bundle_file_size", "zc_bundle_seal", "zc_bundle_seal_host",
-           "zc_bundle_unseal", "zc_bundle_unseal_host"]
+           "zc_bundle_unseal", "zc_bundle_unseal_host", "zc_aes_last_form"]
+ZC_AES_FORM_DECRYPT, ZC_AES_FORM_PLAIN_TABLES, ZC_AES_FORM_LANE, ZC_AES_FORM_AHEAD_1 = 1, 2, 4, 8
+ZC_AES_FORM_CPW_SHIFT = 8
 ZC_BUNDLE_OK, ZC_BUNDLE_BAD_SIZE, ZC_BUNDLE_TRUNCATED = 0, 1, 2
 ZC_BUNDLE_BAD_ADLER1, ZC_BUNDLE_BAD_ADLER2, ZC_BUNDLE_BAD_PADDING = 3, 4, 5
 BUNDLE_STATUS_NAMES = {0: "ok", 1: "bad file size", 2: "truncated", 3: "Adler-32 mismatch after BundleInfo",
@@ -162,6 +164,7 @@ def load(path=LIB_PATH):
         # (ctx, key, files, file_off, file_size, n, plain, plain_off, layout)
         "zc_bundle_unseal": (i32, [vp, vp, vp, vp, vp, sz, vp, vp, vp]),
         "zc_bundle_unseal_host": (i32, [vp, vp, vp, vp, vp, sz, vp, vp, vp]),
+        "zc_aes_last_form": (i32, [vp, ctypes.POINTER(u32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -259,6 +259,15 @@ class BundleCompressor:
                                           ("body_off", "body_len"))))
         return out
 
+    def aes_last_form(self):
+        """The form of the CBC kernel this context launched last (zc_aes_last_form):
+        ZC_AES_FORM_* bits, the lane kernel's chains per wave in bits 8-15.
+        Raises ZcError when it has launched none."""
+        form = ctypes.c_uint32()
+        rc = self._L.zc_aes_last_form(self._ctx, ctypes.byref(form))
+        _check(self._L, self._ctx, rc, "zc_aes_last_form")
+        return form.value
+
     def last_stats(self):
         """(parse kernel ms, 48 KiB blocks) of the last compress()."""
         ms, blocks = ctypes.c_double(), ctypes.c_uint64()

@@ -329,13 +329,53 @@ struct AesScratch {
   Buf<FileDesc> fdesc;
   Buf<zcaes::Parsed> parsed;
   int cus = 0;
+  uint32_t form = 0;  // the CBC kernel last launched (ZC_AES_FORM_*), set where run_cbc launches
+  bool form_set = false;
   AesScratch() { zcaes::make_tables(&tab); }
 };
 
 AesScratch* aes_scratch_new() { return new AesScratch(); }
 void aes_scratch_free(AesScratch* s) { delete s; }
+bool aes_last_form(const AesScratch* s, uint32_t* form) {
+  if (!s || !s->form_set) return false;
+  *form = s->form;
+  return true;
+}
 
 namespace {
+
+void set_form(AesScratch* s, uint32_t form) {
+  s->form = form;
+  s->form_set = true;
+}
+
+// A compiled form: the kernel with the word zc_aes_last_form reports for it.
+// The word is made from the template arguments the kernel pointer is taken
+// with, so it names the instantiation that is launched, whatever selected it.
+template <class K>
+struct Form {
+  K kernel;
+  uint32_t form;
+};
+template <bool REPL>
+constexpr uint32_t table_bit() {
+  return REPL ? 0u : (uint32_t)ZC_AES_FORM_PLAIN_TABLES;
+}
+template <bool REPL, int G>
+constexpr auto enc4_form() {
+  return Form<decltype(&zc_aes_cbc_enc4_kernel<REPL, G>)>{&zc_aes_cbc_enc4_kernel<REPL, G>, table_bit<REPL>()};
+}
+template <bool REPL, int G>
+constexpr auto lane_form() {
+  return Form<decltype(&zc_aes_cbc_enc_kernel<REPL, G>)>{
+      &zc_aes_cbc_enc_kernel<REPL, G>,
+      ZC_AES_FORM_LANE | table_bit<REPL>() | (G == 1 ? (uint32_t)ZC_AES_FORM_AHEAD_1 : 0u)};
+}
+template <bool REPL>
+constexpr auto dec_form() {
+  return Form<decltype(&zc_aes_cbc_dec_kernel<REPL>)>{&zc_aes_cbc_dec_kernel<REPL>,
+                                                      ZC_AES_FORM_DECRYPT | table_bit<REPL>()};
+}
 
 bool shared_tables() {
   const char* e = getenv("ZC_AES_TABLE");
@@ -378,13 +418,10 @@ int run_cbc(AesScratch* s, bool decrypt, const uint8_t* key, const std::vector<A
       ACK(s->d_rk.ensure(zcaes::kRkWords));
       ACK(hipMemcpyAsync(s->d_rk.p, rk.w, sizeof rk.w, hipMemcpyHostToDevice, st));
       const dim3 grid((uint32_t)((4ull * n + 255) / 256)), block(256);
-      if (shared)
-        hipLaunchKernelGGL((zc_aes_cbc_enc4_kernel<false, kEncAhead>), grid, block, 0, st, s->d_rk.p, s->chains.p, n,
-                           s->d_tab.p);
-      else
-        hipLaunchKernelGGL((zc_aes_cbc_enc4_kernel<true, kEncAhead>), grid, block, 0, st, s->d_rk.p, s->chains.p, n,
-                           s->d_tab.p);
+      const auto f = shared ? enc4_form<false, kEncAhead>() : enc4_form<true, kEncAhead>();
+      hipLaunchKernelGGL(f.kernel, grid, block, 0, st, s->d_rk.p, s->chains.p, n, s->d_tab.p);
       ACK(hipGetLastError());
+      set_form(s, f.form);
       ACK(hipStreamSynchronize(st));  // rk's host memory is reused
       return ZC_OK;
     }
@@ -397,10 +434,11 @@ int run_cbc(AesScratch* s, bool decrypt, const uint8_t* key, const std::vector<A
     const dim3 grid((waves + 3) / 4), block(256);
     const char* pf = getenv("ZC_AES_PREFETCH");  // measurements: "1" = one block ahead
     const bool one = pf && !strcmp(pf, "1");
-    auto kernel = shared ? (one ? zc_aes_cbc_enc_kernel<false, 1> : zc_aes_cbc_enc_kernel<false, kEncAhead>)
-                         : (one ? zc_aes_cbc_enc_kernel<true, 1> : zc_aes_cbc_enc_kernel<true, kEncAhead>);
-    hipLaunchKernelGGL(kernel, grid, block, 0, st, rk, s->chains.p, n, cpw, s->d_tab.p);
+    const auto f = shared ? (one ? lane_form<false, 1>() : lane_form<false, kEncAhead>())
+                          : (one ? lane_form<true, 1>() : lane_form<true, kEncAhead>());
+    hipLaunchKernelGGL(f.kernel, grid, block, 0, st, rk, s->chains.p, n, cpw, s->d_tab.p);
     ACK(hipGetLastError());
+    set_form(s, f.form | cpw << ZC_AES_FORM_CPW_SHIFT);  // cpw: the launch's own argument
     ACK(hipStreamSynchronize(st));
     return ZC_OK;
   }
@@ -413,13 +451,10 @@ int run_cbc(AesScratch* s, bool decrypt, const uint8_t* key, const std::vector<A
   ACK(hipMemcpyAsync(s->tiles.p, tiles.data(), tiles.size() * sizeof(AesTile), hipMemcpyHostToDevice, st));
   const uint32_t nt = (uint32_t)tiles.size();
   const dim3 grid(std::min<uint32_t>(nt, 2u * (uint32_t)s->cus)), block(256);
-  if (shared)
-    hipLaunchKernelGGL(zc_aes_cbc_dec_kernel<false>, grid, block, 0, st, rk, s->chains.p, s->tiles.p, nt, s->d_tab.p + 256,
-                       s->d_tab.p + 512);
-  else
-    hipLaunchKernelGGL(zc_aes_cbc_dec_kernel<true>, grid, block, 0, st, rk, s->chains.p, s->tiles.p, nt, s->d_tab.p + 256,
-                       s->d_tab.p + 512);
+  const auto f = shared ? dec_form<false>() : dec_form<true>();
+  hipLaunchKernelGGL(f.kernel, grid, block, 0, st, rk, s->chains.p, s->tiles.p, nt, s->d_tab.p + 256, s->d_tab.p + 512);
   ACK(hipGetLastError());
+  set_form(s, f.form);
   ACK(hipStreamSynchronize(st));  // the lists' host memory is reused
   return ZC_OK;
 }

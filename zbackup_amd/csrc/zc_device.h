@@ -507,6 +507,8 @@ hipError_t lzo_scatter(LzoScratch* s, const uint8_t* d_src, const uint64_t* off,
 struct AesScratch;
 AesScratch* aes_scratch_new();
 void aes_scratch_free(AesScratch* s);
+// the form (ZC_AES_FORM_*) of the CBC kernel s launched last; false when it has launched none
+bool aes_last_form(const AesScratch* s, uint32_t* form);
 int aes_cbc(AesScratch* s, bool decrypt, bool host, const uint8_t* key, const void* in, const uint64_t* in_off,
             const uint64_t* len, size_t n, const uint8_t* iv, void* out, const uint64_t* out_off, hipEvent_t ev_in,
             hipStream_t st, std::string& err);

@@ -4111,6 +4111,17 @@ int zc_aes128_cbc_decrypt_host(zc_ctx* c, const uint8_t key[16], const void* in,
   });
 }
 
+int zc_aes_last_form(const zc_ctx* cc, uint32_t* form) {
+  zc_ctx* c = const_cast<zc_ctx*>(cc);  // the message is the context's
+  ZC_LOCK(c);
+  if (!c) return ctx_arg_error(c, "zc_aes_last_form: null context");
+  if (!form) return ctx_arg_error(c, "zc_aes_last_form: null pointer");
+  if (!aes_last_form(c->aes, form))
+    return ctx_arg_error(c, "zc_aes_last_form: this context has launched no CBC kernel yet");
+  c->err.clear();
+  return ZC_OK;
+}
+
 uint64_t zc_bundle_file_size(uint64_t prefix_len, uint64_t body_len, int keyed) {
   return keyed ? (prefix_len + 4 + body_len + 4) / 16 * 16 + 16 : prefix_len + body_len + 8;
 }
