@@ -46,6 +46,8 @@
  *   zc_bundle_seal         the file Bundle::Creator::write puts through EncryptedFile::OutputStream
  *                                                                bundle.cc:96-155, encrypted_file.cc:239-392
  *   zc_bundle_unseal       the same file read back by Bundle::Reader     bundle.cc:157-218
+ *   zc_gc_plan             ZCollector::gc's loadIndex walk through BundleCollector
+ *                                                                zutils.cc:450-505, backup_collector.cc:17-144
  *   zc_last_error          the DEF_EX exceptions / CHECK aborts of the reference
  *                          (backup_creator.cc:112,165-166, chunk_index.hh:88-89)
  */
@@ -436,6 +438,104 @@ int zc_bundle_unseal(zc_ctx* ctx, const uint8_t* key, const void* d_files, const
 int zc_bundle_unseal_host(zc_ctx* ctx, const uint8_t* key, const void* files, const uint64_t* file_off,
                           const uint64_t* file_size, size_t n, void* plain, const uint64_t* plain_off,
                           zc_bundle_layout* layout);
+
+/* ---- Garbage collection: which chunks are used, which bundles go, what is copied where ----
+ * `zbackup gc` (ZCollector::gc, zutils.cc:450-505) puts every chunk_to_emit id of every backup
+ * into BundleCollector::usedChunkSet, then ChunkIndex::loadIndex (chunk_index.cc:26-79) walks
+ * every chunk record of every index file through the BundleCollector (backup_collector.cc:17-144).
+ * zc_gc_plan is that walk for a whole repository in one call: an exact table of the 24-byte ids in
+ * HBM (zc_gc_core.h) answers the set lookups, the host takes the per-bundle decisions in order.
+ * It plans only: unlinking files, decoding the bundles to repack and writing the new ones
+ * (zc_bundle_gather, zc_lzo_compress, zc_bundle_seal) stay with the caller.  Callers detect these
+ * entry points by their symbols (the ABI version stays 5).
+ *
+ * Processing position.  loadIndex and copyUsedChunks walk a bundle's records from the last to the
+ * first (chunk_index.cc:55, backup_collector.cc:134): record r of bundle b with k records has
+ * position bundle_first[b] + (k-1-r), and "first" below always means the smallest position.
+ *
+ * Per record (record_flags): COUNTED = processChunk went past its gcDeep test (lines 53-59):
+ * always without ZC_GC_DEEP, with it only for the first occurrence of the id over the whole input
+ * (overallChunkSet); USED = the id is in `used` (line 62, line 138); COPIED = the record is in
+ * the copy list.
+ * Per bundle: total = its COUNTED records, used = its COUNTED and USED ones (lines 61-66), and
+ * the action finishBundle takes (lines 69-127), decided in bundle order:
+ *   REMOVE       used == 0 and total != 0                          (lines 74-80)
+ *   REPACK       else used < total, or ZC_GC_REPACK                (lines 81-97)
+ *   REMOVE       else deep, total == 0, bundle id not seen before; the id is now seen (100-109)
+ *   DROP_RECORD  else deep, total == 0, bundle id seen: the index file is rewritten without the
+ *                record, the bundle file is not unlinked           (lines 110-114)
+ *   KEEP         else; under deep the bundle id is now seen        (lines 116-124)
+ * Per index file: total / used = sums over its bundles (lines 72-73), kept / modified_bundles /
+ * removed = its KEEP / REPACK / REMOVE bundles, modified = any bundle not kept, necessary = a
+ * COUNTED record of it is USED (line 65), unlink = modified || (deep && !necessary) || concat
+ * (finishIndex, lines 24-42).
+ * The copy list: for every REPACK bundle in order, its USED records in processing order,
+ * COUNTED or not (copyUsedChunks, lines 129-144), except those whose id an earlier entry of the
+ * list has (Writer::add -> ChunkIndex::addChunk on the fresh reindex, chunk_storage.cc:31-46,
+ * chunk_index.cc:185-202).  copy[k] = the record, copy_bundle[k] = its new bundle by Writer::add's
+ * rule with max_payload (zc_bundle_plan), copy_off[k] = its offset in that bundle's payload.
+ * finishIndex ends the current new bundle (commit() / reset(), chunk_storage.cc:61-104), so no
+ * new bundle spans two index files: new_bundle_index[j] = the index file of new bundle j,
+ * new_bundle_size[j] = its payload bytes.
+ *
+ * ZC_ERR_ARG, with a message in zc_last_error: a NULL pointer; bundle_first / index_first not
+ * starting at 0, decreasing, or not ending at n_records / n_bundles; a count of 2^32 - 1 or more;
+ * an unknown flag -- all found before the context is looked at --; two records with the same id and
+ * different sizes (the reference reads a copied chunk through the old index's first registration,
+ * so such an input has no defined result; found on the device, reported after the first phase);
+ * copy_cap or new_bundle_cap too small (n_copy / n_new_bundles then hold the counts needed; the
+ * other outputs are complete).  Zero records, bundles, index files and used ids are all legal. */
+enum { ZC_GC_DEEP = 1u, ZC_GC_REPACK = 2u, ZC_GC_CONCAT = 4u };  /* --gc-deep, gc.repack, gc.concat */
+enum { ZC_GC_ACT_KEEP = 0, ZC_GC_ACT_REMOVE = 1, ZC_GC_ACT_REPACK = 2, ZC_GC_ACT_DROP_RECORD = 3 };
+enum { ZC_GC_REC_COUNTED = 1u, ZC_GC_REC_USED = 2u, ZC_GC_REC_COPIED = 4u };
+typedef struct zc_gc_input {
+  const uint8_t* ids;            /* n_records x 24: every chunk record of every index file, in the */
+  const uint32_t* sizes;         /*   order read: index file, bundle, BundleInfo.chunk_record(0..k-1) */
+  uint64_t n_records;
+  const uint64_t* bundle_first;  /* n_bundles + 1: bundle b's records are [bundle_first[b], bundle_first[b+1]) */
+  const uint8_t* bundle_ids;     /* n_bundles x 24 */
+  uint64_t n_bundles;
+  const uint64_t* index_first;   /* n_indexes + 1: index file i's bundles */
+  uint64_t n_indexes;
+  const uint8_t* used;           /* n_used x 24: the ids the backups emit; duplicates and strangers allowed */
+  uint64_t n_used;
+  uint32_t flags;                /* ZC_GC_DEEP | ZC_GC_REPACK | ZC_GC_CONCAT */
+  uint32_t reserved;
+  uint64_t max_payload;          /* bundle.max_payload_size */
+} zc_gc_input;
+typedef struct zc_gc_index {
+  uint64_t total, used;                       /* indexTotalChunks, indexUsedChunks */
+  uint32_t kept, modified_bundles, removed;   /* indexKeptBundles, indexModifiedBundles, indexRemovedBundles */
+  uint8_t modified, necessary, unlink, reserved;
+} zc_gc_index;
+typedef struct zc_gc_output {
+  uint8_t* record_flags;       /* n_records: ZC_GC_REC_* */
+  uint32_t* bundle_total;      /* n_bundles each */
+  uint32_t* bundle_used;
+  uint8_t* bundle_action;      /* ZC_GC_ACT_* */
+  zc_gc_index* indexes;        /* n_indexes */
+  uint32_t* copy;              /* copy_cap each */
+  uint32_t* copy_bundle;
+  uint64_t* copy_off;
+  uint64_t copy_cap;
+  uint64_t n_copy;             /* out */
+  uint32_t* new_bundle_index;  /* new_bundle_cap each */
+  uint64_t* new_bundle_size;
+  uint64_t new_bundle_cap;
+  uint64_t n_new_bundles;      /* out */
+} zc_gc_output;
+int zc_gc_plan(zc_ctx* ctx, const zc_gc_input* in, zc_gc_output* out);
+/* The last zc_gc_plan of the context: device time of the table build (records into processing
+ * order, insert) and of the probes (used ids, per-record flags, per-bundle counts), the table's
+ * slots (a power of two, at least twice the records; ZC_TEST_GC_BITS=<b> in the environment makes
+ * it 2^b when that is smaller and still leaves a free slot: tests only) and the longest probe run
+ * any insert or lookup walked. */
+int zc_gc_last_stats(const zc_ctx* ctx, double* build_ms, double* probe_ms, uint64_t* table_slots,
+                     uint32_t* max_probe);
+/* the rest of that call's time: the upload, the host's own steps (the decisions between the
+ * phases, the bundling rule over the copy list at the end), the second phase's kernels (candidate
+ * insert, compaction), both read-backs with the waits for the device */
+int zc_gc_last_times(const zc_ctx* ctx, double* upload_ms, double* host_ms, double* copy_ms, double* readback_ms);
 
 int zc_abi_version(void);
 /* digest of the sources this library was built from (zbackup_amd/_build.py

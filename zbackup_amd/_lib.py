@@ -24,7 +24,11 @@ EXPORTS = ["zc_create", "zc_destroy", "zc_seed_index", "zc_get_input_buffer",
            "zc_lzo_frame_info", "zc_bundle_scatter", "zc_parse_instructions",
            "zc_aes128_cbc_encrypt", "zc_aes128_cbc_decrypt", "zc_aes128_cbc_encrypt_host",
            "zc_aes128_cbc_decrypt_host", "zc_bundle_file_size", "zc_bundle_seal", "zc_bundle_seal_host",
-           "zc_bundle_unseal", "zc_bundle_unseal_host", "zc_aes_last_form"]
+           "zc_bundle_unseal", "zc_bundle_unseal_host", "zc_aes_last_form",
+           "zc_gc_plan", "zc_gc_last_stats", "zc_gc_last_times"]
+ZC_GC_DEEP, ZC_GC_REPACK, ZC_GC_CONCAT = 1, 2, 4
+ZC_GC_ACT_KEEP, ZC_GC_ACT_REMOVE, ZC_GC_ACT_REPACK, ZC_GC_ACT_DROP_RECORD = 0, 1, 2, 3
+ZC_GC_REC_COUNTED, ZC_GC_REC_USED, ZC_GC_REC_COPIED = 1, 2, 4
 ZC_AES_FORM_DECRYPT, ZC_AES_FORM_PLAIN_TABLES, ZC_AES_FORM_LANE, ZC_AES_FORM_AHEAD_1 = 1, 2, 4, 8
 ZC_AES_FORM_CPW_SHIFT = 8
 ZC_BUNDLE_OK, ZC_BUNDLE_BAD_SIZE, ZC_BUNDLE_TRUNCATED = 0, 1, 2
@@ -66,6 +70,29 @@ class ZcBundleLayout(ctypes.Structure):
     _fields_ = [("status", ctypes.c_int32), ("reserved", ctypes.c_uint32), ("header_off", ctypes.c_uint64),
                 ("header_len", ctypes.c_uint64), ("info_off", ctypes.c_uint64), ("info_len", ctypes.c_uint64),
                 ("body_off", ctypes.c_uint64), ("body_len", ctypes.c_uint64)]
+
+
+class ZcGcInput(ctypes.Structure):
+    _fields_ = [("ids", ctypes.c_void_p), ("sizes", ctypes.c_void_p), ("n_records", ctypes.c_uint64),
+                ("bundle_first", ctypes.c_void_p), ("bundle_ids", ctypes.c_void_p), ("n_bundles", ctypes.c_uint64),
+                ("index_first", ctypes.c_void_p), ("n_indexes", ctypes.c_uint64),
+                ("used", ctypes.c_void_p), ("n_used", ctypes.c_uint64),
+                ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("max_payload", ctypes.c_uint64)]
+
+
+class ZcGcIndex(ctypes.Structure):
+    _fields_ = [("total", ctypes.c_uint64), ("used", ctypes.c_uint64), ("kept", ctypes.c_uint32),
+                ("modified_bundles", ctypes.c_uint32), ("removed", ctypes.c_uint32), ("modified", ctypes.c_uint8),
+                ("necessary", ctypes.c_uint8), ("unlink", ctypes.c_uint8), ("reserved", ctypes.c_uint8)]
+
+
+class ZcGcOutput(ctypes.Structure):
+    _fields_ = [("record_flags", ctypes.c_void_p), ("bundle_total", ctypes.c_void_p),
+                ("bundle_used", ctypes.c_void_p), ("bundle_action", ctypes.c_void_p), ("indexes", ctypes.c_void_p),
+                ("copy", ctypes.c_void_p), ("copy_bundle", ctypes.c_void_p), ("copy_off", ctypes.c_void_p),
+                ("copy_cap", ctypes.c_uint64), ("n_copy", ctypes.c_uint64),
+                ("new_bundle_index", ctypes.c_void_p), ("new_bundle_size", ctypes.c_void_p),
+                ("new_bundle_cap", ctypes.c_uint64), ("n_new_bundles", ctypes.c_uint64)]
 
 
 class ZcStats(ctypes.Structure):
@@ -165,6 +192,11 @@ def load(path=LIB_PATH):
         "zc_bundle_unseal": (i32, [vp, vp, vp, vp, vp, sz, vp, vp, vp]),
         "zc_bundle_unseal_host": (i32, [vp, vp, vp, vp, vp, sz, vp, vp, vp]),
         "zc_aes_last_form": (i32, [vp, ctypes.POINTER(u32)]),
+        # garbage collection
+        "zc_gc_plan": (i32, [vp, ctypes.POINTER(ZcGcInput), ctypes.POINTER(ZcGcOutput)]),
+        "zc_gc_last_stats": (i32, [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                   ctypes.POINTER(u64), ctypes.POINTER(u32)]),
+        "zc_gc_last_times": (i32, [vp] + [ctypes.POINTER(ctypes.c_double)] * 4),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -10,6 +10,8 @@
 
 struct zc_bundle_file;    // include/zchunk.h
 struct zc_bundle_layout;
+struct zc_gc_input;
+struct zc_gc_output;
 
 namespace zc {
 
@@ -519,5 +521,20 @@ int bundle_unseal(AesScratch* s, LzoScratch* lz, bool host, const uint8_t* key, 
                   const uint64_t* file_off, const uint64_t* file_size, size_t n, void* plain,
                   const uint64_t* plain_off, zc_bundle_layout* layout, hipEvent_t ev_in, hipStream_t st,
                   std::string& err);
+
+// zc_gc.hip: garbage collection's id table and repack plan (zc_gc_core.h).
+// gc_validate checks what the host can see (no device, no context); gc_plan
+// returns a zc_status with its message in `err`.
+struct GcScratch;
+struct GcTimes {
+  double upload_ms, build_ms, probe_ms, host_ms, copy_ms, readback_ms;
+  uint64_t table_slots;
+  uint32_t max_probe;
+};
+GcScratch* gc_scratch_new();
+void gc_scratch_free(GcScratch* s);
+const GcTimes* gc_times(const GcScratch* s);
+int gc_validate(const zc_gc_input* in, const zc_gc_output* out, std::string& err);
+int gc_plan(GcScratch* s, const zc_gc_input* in, zc_gc_output* out, hipStream_t st, std::string& err);
 
 }  // namespace zc

@@ -522,6 +522,7 @@ struct zc_ctx {
   LzoScratch* lzo = nullptr;  // bundle compression (zc_lzo.hip), made on first use
   DevBuf<uint8_t> lzo_in, lzo_out;  // zc_lzo_compress_host's device copies
   AesScratch* aes = nullptr;  // AES-128-CBC and bundle files (zc_aes.hip), made on first use
+  GcScratch* gc = nullptr;    // garbage collection's tables (zc_gc.hip), made on first use
 
   // scratch
   DevBuf<uint64_t> hm_key, hm_fp, hm_rkey;  // metadata of chunks joining the historic index
@@ -3302,6 +3303,7 @@ int zc_destroy(zc_ctx* c) {
     if (c->copy_stream) (void)hipStreamDestroy(c->copy_stream);
     lzo_scratch_free(c->lzo);
     aes_scratch_free(c->aes);
+    gc_scratch_free(c->gc);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     if (prev >= 0) (void)hipSetDevice(prev);
@@ -4162,4 +4164,52 @@ int zc_bundle_unseal_host(zc_ctx* c, const uint8_t* key, const void* files, cons
     return bundle_unseal(c->aes, c->lzo, true, key, files, file_off, file_size, n, plain, plain_off, layout, nullptr,
                          c->stream, err);
   });
+}
+
+// ---- garbage collection: the id table and the repack plan (zc_gc.hip) ----
+
+int zc_gc_plan(zc_ctx* c, const zc_gc_input* in, zc_gc_output* out) {
+  ZC_LOCK(c);
+  // what the host can see is checked before the context is looked at
+  std::string err;
+  int rc = gc_validate(in, out, err);
+  if (rc != ZC_OK) return ctx_arg_error(c, ("zc_gc_plan: " + err).c_str());
+  if (!c) return ctx_arg_error(c, "zc_gc_plan: null context");
+  try {
+    DeviceGuard g(c->device);
+    if (!c->gc) c->gc = gc_scratch_new();
+    rc = gc_plan(c->gc, in, out, c->stream, err);
+  } catch (const ZcError& e) {
+    return fail(c, e);
+  } catch (const std::bad_alloc&) {
+    return fail(c, ZcError{ZC_ERR_NOMEM, "host allocation failed"});
+  }
+  if (rc != ZC_OK)
+    c->err = "zc_gc_plan: " + err;
+  else
+    c->err.clear();
+  return rc;
+}
+
+int zc_gc_last_stats(const zc_ctx* c, double* build_ms, double* probe_ms, uint64_t* table_slots,
+                     uint32_t* max_probe) {
+  ZC_LOCK(c);
+  if (!c) return host_arg_error("zc_gc_last_stats: null context");
+  const GcTimes t = c->gc ? *gc_times(c->gc) : GcTimes{};
+  if (build_ms) *build_ms = t.build_ms;
+  if (probe_ms) *probe_ms = t.probe_ms;
+  if (table_slots) *table_slots = t.table_slots;
+  if (max_probe) *max_probe = t.max_probe;
+  return ZC_OK;
+}
+
+int zc_gc_last_times(const zc_ctx* c, double* upload_ms, double* host_ms, double* copy_ms, double* readback_ms) {
+  ZC_LOCK(c);
+  if (!c) return host_arg_error("zc_gc_last_times: null context");
+  const GcTimes t = c->gc ? *gc_times(c->gc) : GcTimes{};
+  if (upload_ms) *upload_ms = t.upload_ms;
+  if (host_ms) *host_ms = t.host_ms;
+  if (copy_ms) *copy_ms = t.copy_ms;
+  if (readback_ms) *readback_ms = t.readback_ms;
+  return ZC_OK;
 }
