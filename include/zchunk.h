@@ -48,6 +48,9 @@
  *   zc_bundle_unseal       the same file read back by Bundle::Reader     bundle.cc:157-218
  *   zc_gc_plan             ZCollector::gc's loadIndex walk through BundleCollector
  *                                                                zutils.cc:450-505, backup_collector.cc:17-144
+ *   zc_chunk_meta_compute  no counterpart: the metadata of zc_export_chunk_meta and the full
+ *                          ChunkId (chunk_id.hh:16-32, made at backup_creator.cc:127-141) of chunks
+ *                          read back out of decoded bundles (Bundle::Reader::get, bundle.cc:235-251)
  *   zc_last_error          the DEF_EX exceptions / CHECK aborts of the reference
  *                          (backup_creator.cc:112,165-166, chunk_index.hh:88-89)
  */
@@ -536,6 +539,36 @@ int zc_gc_last_stats(const zc_ctx* ctx, double* build_ms, double* probe_ms, uint
  * phases, the bundling rule over the copy list at the end), the second phase's kernels (candidate
  * insert, compaction), both read-backs with the waits for the device */
 int zc_gc_last_times(const zc_ctx* ctx, double* upload_ms, double* host_ms, double* copy_ms, double* readback_ms);
+
+/* ---- Adopting an existing repository: chunk metadata and id check from bundles ----
+ * A repository stock zbackup wrote is known by chunk id only, and ids alone go through the exact
+ * screen at every byte.  The zc_chunk_meta record that lets an id take the anchor path is a pure
+ * function of the chunk's bytes, so it can be computed from the decoded payloads of the
+ * repository's bundles (decoding them is the caller's, as for restore; so is reading BundleInfo:
+ * the caller passes where each chunk lies).  Chunk i is payload[off[i] ..+ size[i]): any byte
+ * offset, any size from 1 up, extents in any order, overlapping or not.  out[i] receives its
+ * record under the context's chunk.max_size W (zc_meta_core.h is the definition): the computed
+ * ChunkId (SHA-1 prefix + RollingHash digest), its size, zc_anchor_def(W), and -- for size == W
+ * only, as zc_export_chunk_meta -- the first content anchor; ZC_META_NO_ANCHOR otherwise.
+ * The same pass checks the bundles: with expect[i] the id and size the bundle claims, status[i]
+ * receives what differs (ZC_META_BAD_*; 0 without expect) and *n_bad the chunks with a status
+ * other than 0.  A mismatch is not an error of the call, and out[i] always carries the computed
+ * id.  Records whose status is 0 and whose size is W are what zc_seed_index_meta takes.
+ * ZC_ERR_ARG, with a message in zc_last_error and before any device work: a NULL payload, off,
+ * size or out with n > 0; size[i] == 0; a chunk that ends past payload_bytes; expect given
+ * with neither status nor n_bad.  n == 0 is ZC_OK.  Callers detect these entry points by their
+ * symbols (the ABI version stays 5). */
+enum { ZC_META_BAD_SHA1 = 1, ZC_META_BAD_ROLLING = 2, ZC_META_BAD_SIZE = 4 };
+int zc_chunk_meta_compute(zc_ctx* ctx, const void* d_payload, uint64_t payload_bytes, const uint64_t* off,
+                          const uint32_t* size, size_t n, const zc_seed* expect, zc_chunk_meta* out,
+                          uint8_t* status, size_t* n_bad);
+/* the same with the payload in host memory (copied to HBM first) */
+int zc_chunk_meta_compute_host(zc_ctx* ctx, const void* payload, uint64_t payload_bytes, const uint64_t* off,
+                               const uint32_t* size, size_t n, const zc_seed* expect, zc_chunk_meta* out,
+                               uint8_t* status, size_t* n_bad);
+/* The context's last such call: device time of the rolling-hash / anchor kernel and of the SHA-1
+ * kernel, and the whole call's wall clock (uploads, both read-backs and the wait included). */
+int zc_meta_last_stats(const zc_ctx* ctx, double* meta_ms, double* sha1_ms, double* total_ms);
 
 int zc_abi_version(void);
 /* digest of the sources this library was built from (zbackup_amd/_build.py

@@ -143,6 +143,15 @@ public:
       return std::string();
     std::vector< zc_chunk_meta > meta( n );
     zcCheck( zc_export_chunk_meta( ctx, meta.data(), meta.size(), &n ), ctx, "zc_export_chunk_meta" );
+    return write( dir, meta );
+  }
+
+  /// the same for records from anywhere (GpuRepositoryAdopter's, say)
+  static std::string write( std::string const & dir, std::vector< zc_chunk_meta > const & meta )
+  {
+    size_t n = meta.size();
+    if ( !n )
+      return std::string();
     std::string data( "ZCMETA01", 8 );
     uint32_t words[ 2 ] = { (uint32_t)sizeof( zc_chunk_meta ), 0 };
     uint64_t count = n;
@@ -637,6 +646,133 @@ public:
       opened[ i ].body.assign( plain, off[ i ] + layout[ i ].body_off, layout[ i ].body_len );
     }
   }
+};
+
+/// Adopting a repository stock zbackup wrote: its chunks are known by id only,
+/// and ids alone go through the exact screen at every byte.  This computes the
+/// chunk metadata (zc_chunk_meta) of every chunk of the bundles handed to it
+/// from their decoded payloads -- Bundle::Reader's, bundle.cc:157-251 -- and
+/// compares each recomputed ChunkId with the one BundleInfo claims, a check of
+/// the bundles zbackup itself does not have.  Payloads are collected and go
+/// through zc_chunk_meta_compute_host every 256 MiB; finish() writes the records
+/// of the chunks that are chunk.max_size bytes and whose id holds as one
+/// GpuChunkMetaSidecar file, which GpuChunkIndex picks up on the next open.
+class GpuRepositoryAdopter: NoCopy
+{
+public:
+  struct Mismatch
+  {
+    Bundle::Id bundle;
+    uint32_t chunk;   // index in the bundle's BundleInfo
+    uint8_t status;   // ZC_META_BAD_* bits
+  };
+
+private:
+  zc_ctx * ctx;
+  uint32_t maxSize;
+  std::string payloads;
+  std::vector< uint64_t > off;
+  std::vector< uint32_t > size, chunkOf;
+  std::vector< zc_seed > expect;
+  std::vector< Bundle::Id > bundleOf;
+  std::vector< zc_chunk_meta > meta;
+  std::vector< Mismatch > bad;
+  uint64_t chunks, bytes;
+
+  void flush()
+  {
+    if ( off.empty() )
+      return;
+    std::vector< zc_chunk_meta > out( off.size() );
+    std::vector< uint8_t > status( off.size() );
+    size_t nBad = 0;
+    zcCheck( zc_chunk_meta_compute_host( ctx, payloads.data(), payloads.size(), off.data(), size.data(), off.size(),
+                                         expect.data(), out.data(), status.data(), &nBad ),
+             ctx, "zc_chunk_meta_compute_host" );
+    for ( size_t i = 0; i < out.size(); ++i )
+      if ( status[ i ] )
+      {
+        Mismatch m = { bundleOf[ i ], chunkOf[ i ], status[ i ] };
+        bad.push_back( m );
+      }
+      else if ( out[ i ].size == maxSize )
+        meta.push_back( out[ i ] );
+    payloads.clear();
+    off.clear();
+    size.clear();
+    chunkOf.clear();
+    expect.clear();
+    bundleOf.clear();
+  }
+
+public:
+  enum { FlushBytes = 256 << 20 };
+
+  GpuRepositoryAdopter( Config const & config, int device ):
+    ctx( 0 ), maxSize( config.GET_STORABLE( chunk, max_size ) ), chunks( 0 ), bytes( 0 )
+  {
+    zcCheck( zc_create( &ctx, maxSize, device, 0 ), 0, "zc_create" );
+  }
+  ~GpuRepositoryAdopter() { zc_destroy( ctx ); }
+
+  /// one bundle: its id, its BundleInfo (chunk_record( i ).id() / .size(), as
+  /// Bundle::Reader reads them: bundle.cc:220-232) and its decoded payload.
+  /// (A template only so that this header asks nothing more of zbackup.pb.h in
+  /// translation units that do not adopt.)
+  template< class Info >
+  void addBundle( Bundle::Id const & id, Info const & info, std::string const & payload )
+  {
+    uint64_t pos = payloads.size(), total = 0;
+    for ( int i = 0; i < info.chunk_record_size(); ++i )
+    {
+      std::string const & blob = info.chunk_record( i ).id();
+      if ( blob.size() != 24 )
+        throw std::runtime_error( "adopt: a chunk id that is not 24 bytes" );
+      zc_seed s;
+      memcpy( s.sha1, blob.data(), 16 );
+      memcpy( &s.rolling, blob.data() + 16, 8 );  // ChunkId::setFromBlob, chunk_id.cc:29-38 (little-endian host)
+      s.size = info.chunk_record( i ).size();
+      s.reserved = 0;
+      off.push_back( pos + total );
+      size.push_back( s.size );
+      chunkOf.push_back( (uint32_t)i );
+      expect.push_back( s );
+      bundleOf.push_back( id );
+      total += s.size;
+    }
+    if ( total != payload.size() )
+    {
+      size_t n = (size_t)info.chunk_record_size();
+      off.resize( off.size() - n );
+      size.resize( size.size() - n );
+      chunkOf.resize( chunkOf.size() - n );
+      expect.resize( expect.size() - n );
+      bundleOf.resize( bundleOf.size() - n );
+      throw std::runtime_error( "adopt: a bundle's payload is not the sum of its chunk sizes" );
+    }
+    payloads.append( payload );
+    chunks += (uint64_t)info.chunk_record_size();
+    bytes += total;
+    if ( payloads.size() >= (size_t)FlushBytes )
+      flush();
+  }
+
+  /// the rest through the GPU, then one sidecar file in metaDir ("" when no
+  /// chunk qualified); returns every chunk whose recomputed id or size differs
+  std::vector< Mismatch > finish( std::string const & metaDir, std::string * path = 0 )
+  {
+    flush();
+    std::string p = GpuChunkMetaSidecar::write( metaDir, meta );
+    if ( path )
+      *path = p;
+    meta.clear();
+    std::vector< Mismatch > out;
+    out.swap( bad );
+    return out;
+  }
+
+  uint64_t chunksSeen() const { return chunks; }
+  uint64_t bytesSeen() const { return bytes; }
 };
 
 #endif

@@ -25,7 +25,9 @@ EXPORTS = ["zc_create", "zc_destroy", "zc_seed_index", "zc_get_input_buffer",
            "zc_aes128_cbc_encrypt", "zc_aes128_cbc_decrypt", "zc_aes128_cbc_encrypt_host",
            "zc_aes128_cbc_decrypt_host", "zc_bundle_file_size", "zc_bundle_seal", "zc_bundle_seal_host",
            "zc_bundle_unseal", "zc_bundle_unseal_host", "zc_aes_last_form",
-           "zc_gc_plan", "zc_gc_last_stats", "zc_gc_last_times"]
+           "zc_gc_plan", "zc_gc_last_stats", "zc_gc_last_times",
+           "zc_chunk_meta_compute", "zc_chunk_meta_compute_host", "zc_meta_last_stats"]
+ZC_META_BAD_SHA1, ZC_META_BAD_ROLLING, ZC_META_BAD_SIZE = 1, 2, 4
 ZC_GC_DEEP, ZC_GC_REPACK, ZC_GC_CONCAT = 1, 2, 4
 ZC_GC_ACT_KEEP, ZC_GC_ACT_REMOVE, ZC_GC_ACT_REPACK, ZC_GC_ACT_DROP_RECORD = 0, 1, 2, 3
 ZC_GC_REC_COUNTED, ZC_GC_REC_USED, ZC_GC_REC_COPIED = 1, 2, 4
@@ -197,6 +199,10 @@ def load(path=LIB_PATH):
         "zc_gc_last_stats": (i32, [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                    ctypes.POINTER(u64), ctypes.POINTER(u32)]),
         "zc_gc_last_times": (i32, [vp] + [ctypes.POINTER(ctypes.c_double)] * 4),
+        # adoption: (ctx, payload, payload_bytes, off, size, n, expect, out, status, n_bad)
+        "zc_chunk_meta_compute": (i32, [vp, vp, u64, vp, vp, sz, vp, vp, vp, ctypes.POINTER(sz)]),
+        "zc_chunk_meta_compute_host": (i32, [vp, vp, u64, vp, vp, sz, vp, vp, vp, ctypes.POINTER(sz)]),
+        "zc_meta_last_stats": (i32, [vp] + [ctypes.POINTER(ctypes.c_double)] * 3),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

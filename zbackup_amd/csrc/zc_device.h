@@ -8,6 +8,8 @@
 
 #include <string>
 
+#include "../../include/zchunk.h"  // zc_seed, zc_chunk_meta (typedefs of unnamed structs)
+
 struct zc_bundle_file;    // include/zchunk.h
 struct zc_bundle_layout;
 struct zc_gc_input;
@@ -536,5 +538,24 @@ void gc_scratch_free(GcScratch* s);
 const GcTimes* gc_times(const GcScratch* s);
 int gc_validate(const zc_gc_input* in, const zc_gc_output* out, std::string& err);
 int gc_plan(GcScratch* s, const zc_gc_input* in, zc_gc_output* out, hipStream_t st, std::string& err);
+
+// zc_meta.hip: chunk metadata and id check from bytes wherever they lie
+// (zc_meta_core.h).  meta_validate checks what the host can see (no device, no
+// context); meta_compute returns a zc_status with its message in `err`.
+struct MetaScratch;
+struct MetaTimes {
+  double meta_ms, sha1_ms, total_ms;
+};
+MetaScratch* meta_scratch_new();
+void meta_scratch_free(MetaScratch* s);
+const MetaTimes* meta_times(const MetaScratch* s);
+int meta_validate(const void* payload, uint64_t payload_bytes, const uint64_t* off, const uint32_t* size, size_t n,
+                  const zc_seed* expect, const zc_chunk_meta* out, const uint8_t* status, const size_t* n_bad,
+                  std::string& err);
+// host: the payload is in host memory (copied to HBM first); else ev_in orders
+// the context stream after the legacy default stream.  def: zc_anchor_def(W)
+int meta_compute(MetaScratch* s, bool host, const void* payload, uint64_t payload_bytes, const uint64_t* off,
+                 const uint32_t* size, size_t n, uint32_t W, uint32_t def, const zc_seed* expect, zc_chunk_meta* out,
+                 uint8_t* status, size_t* n_bad, hipEvent_t ev_in, hipStream_t st, std::string& err);
 
 }  // namespace zc

@@ -523,6 +523,7 @@ struct zc_ctx {
   DevBuf<uint8_t> lzo_in, lzo_out;  // zc_lzo_compress_host's device copies
   AesScratch* aes = nullptr;  // AES-128-CBC and bundle files (zc_aes.hip), made on first use
   GcScratch* gc = nullptr;    // garbage collection's tables (zc_gc.hip), made on first use
+  MetaScratch* meta = nullptr;  // adoption's buffers (zc_meta.hip), made on first use
 
   // scratch
   DevBuf<uint64_t> hm_key, hm_fp, hm_rkey;  // metadata of chunks joining the historic index
@@ -3304,6 +3305,7 @@ int zc_destroy(zc_ctx* c) {
     lzo_scratch_free(c->lzo);
     aes_scratch_free(c->aes);
     gc_scratch_free(c->gc);
+    meta_scratch_free(c->meta);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     if (prev >= 0) (void)hipSetDevice(prev);
@@ -4211,5 +4213,63 @@ int zc_gc_last_times(const zc_ctx* c, double* upload_ms, double* host_ms, double
   if (host_ms) *host_ms = t.host_ms;
   if (copy_ms) *copy_ms = t.copy_ms;
   if (readback_ms) *readback_ms = t.readback_ms;
+  return ZC_OK;
+}
+
+// ---- adoption: chunk metadata and id check from decoded bundle payloads (zc_meta.hip) ----
+
+static int meta_entry(zc_ctx* c, const char* what, bool host, const void* payload, uint64_t payload_bytes,
+                      const uint64_t* off, const uint32_t* size, size_t n, const zc_seed* expect, zc_chunk_meta* out,
+                      uint8_t* status, size_t* n_bad) {
+  // what the host can see is checked before the context is looked at
+  std::string err;
+  int rc = meta_validate(payload, payload_bytes, off, size, n, expect, out, status, n_bad, err);
+  if (rc != ZC_OK) return ctx_arg_error(c, (std::string(what) + ": " + err).c_str());
+  if (!c) return ctx_arg_error(c, (std::string(what) + ": null context").c_str());
+  if (n_bad) *n_bad = 0;
+  if (!n) {
+    c->err.clear();
+    return ZC_OK;
+  }
+  try {
+    DeviceGuard g(c->device);
+    if (!c->meta) c->meta = meta_scratch_new();
+    rc = meta_compute(c->meta, host, payload, payload_bytes, off, size, n, c->W, anchor_def_of(c->W), expect, out,
+                      status, n_bad, c->ev_in, c->stream, err);
+  } catch (const ZcError& e) {
+    return fail(c, e);
+  } catch (const std::bad_alloc&) {
+    return fail(c, ZcError{ZC_ERR_NOMEM, "host allocation failed"});
+  }
+  if (rc != ZC_OK)
+    c->err = std::string(what) + ": " + err;
+  else
+    c->err.clear();
+  return rc;
+}
+
+int zc_chunk_meta_compute(zc_ctx* c, const void* d_payload, uint64_t payload_bytes, const uint64_t* off,
+                          const uint32_t* size, size_t n, const zc_seed* expect, zc_chunk_meta* out, uint8_t* status,
+                          size_t* n_bad) {
+  ZC_LOCK(c);
+  return meta_entry(c, "zc_chunk_meta_compute", false, d_payload, payload_bytes, off, size, n, expect, out, status,
+                    n_bad);
+}
+
+int zc_chunk_meta_compute_host(zc_ctx* c, const void* payload, uint64_t payload_bytes, const uint64_t* off,
+                               const uint32_t* size, size_t n, const zc_seed* expect, zc_chunk_meta* out,
+                               uint8_t* status, size_t* n_bad) {
+  ZC_LOCK(c);
+  return meta_entry(c, "zc_chunk_meta_compute_host", true, payload, payload_bytes, off, size, n, expect, out, status,
+                    n_bad);
+}
+
+int zc_meta_last_stats(const zc_ctx* c, double* meta_ms, double* sha1_ms, double* total_ms) {
+  ZC_LOCK(c);
+  if (!c) return host_arg_error("zc_meta_last_stats: null context");
+  const MetaTimes t = c->meta ? *meta_times(c->meta) : MetaTimes{};
+  if (meta_ms) *meta_ms = t.meta_ms;
+  if (sha1_ms) *sha1_ms = t.sha1_ms;
+  if (total_ms) *total_ms = t.total_ms;
   return ZC_OK;
 }
