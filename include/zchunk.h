@@ -229,6 +229,20 @@ int zc_get_records(const zc_ctx* ctx, zc_record* out, size_t cap, size_t* n_out)
 /* move up to cap complete records out of the context, in stream order */
 int zc_take_records(zc_ctx* ctx, zc_record* out, size_t cap, size_t* n_out);
 int zc_get_stats(const zc_ctx* ctx, zc_stats* out);
+/* Which code paths the context's last stream took, OR-ed over the epochs and passes of the last
+ * zc_chunk_device / zc_chunk_host / zc_finish (a fed stream's window segments included); kept
+ * across zc_reset.  For tests of a context that lives through many streams (the epoch tables,
+ * their "clean" flag and the scan-written key arrays outlive a stream); a caller needs none of
+ * it.  ZC_ERR_ARG for a NULL pointer, ZC_ERR_STATE (with a message in zc_last_error) before the
+ * context has finished a stream. */
+enum {
+  ZC_PATH_FUSED_INSERT = 1,            /* the first epoch's index launch took the fused form: tables found
+                                        * clear, every grid key from the scan, inserts in the metadata kernel */
+  ZC_PATH_SCAN_KEYS = 2,               /* an epoch took grid keys the scan had written (key_from > 0) */
+  ZC_PATH_TABLES_REALLOCATED = 4,      /* an epoch table (class table, anchor table, filter) was reallocated */
+  ZC_PATH_TABLES_CLEARED_BY_EPOCH = 8  /* an index launch cleared the tables itself (the non-fused form) */
+};
+int zc_last_stream_paths(const zc_ctx* ctx, uint32_t* bits);
 int zc_reset(zc_ctx* ctx); /* begin a new stream (the seeded index is kept) */
 /* drop the index entries this context's streams added (ZC_FLAG_SHA1: Writer::add ->
  * ChunkIndex::addChunk, chunk_storage.cc:31-46), keeping the seeded ones.  Only for streams

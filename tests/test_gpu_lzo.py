@@ -96,6 +96,35 @@ def test_lzo_repeated_calls_reuse_dictionaries(torch_cuda, comp):
         _check(payloads, _compress(torch_cuda, comp, payloads, rng))
 
 
+@pytest.mark.parametrize("batch_blocks", [None, "3"])
+def test_lzo_generation_wrap(torch_cuda, monkeypatch, batch_blocks):
+    """The dictionaries' 16-bit generation tag wraps after 65,535 batches of one
+    context, and the dictionaries are zeroed there (lzo_batch).  A new
+    compressor starts at generation 65532 (ZC_TEST_LZO_GEN0): eight calls of
+    equal sizes (the dictionaries are never reallocated) run through tags
+    65533, 65534, 65535, the clear, 1, 2, ...; with batches of at most 3 blocks
+    every payload is a batch of its own and the wrap falls inside the first
+    call.  Each call's payloads are the call's before with every 4,096th byte
+    changed, so an entry a stale tag let through would point at bytes that
+    almost match.  Every frame byte-identical to liblzo2's."""
+    from zbackup_amd.bundle import BundleCompressor
+    monkeypatch.setenv("ZC_TEST_LZO_GEN0", "65532")
+    if batch_blocks is None:
+        monkeypatch.delenv("ZC_LZO_BATCH_BLOCKS", raising=False)
+    else:
+        monkeypatch.setenv("ZC_LZO_BATCH_BLOCKS", batch_blocks)
+    rng = np.random.default_rng(10)
+    payloads = [payload(k, 150000, 1000 + j) for j, k in enumerate(KINDS)]
+    assert len(payloads) == 6
+    with BundleCompressor() as c:  # (its scratch, made by its first call, reads the variable)
+        for call in range(8):
+            _check(payloads, _compress(torch_cuda, c, payloads, rng))
+            nxt = [p.copy() for p in payloads]
+            for p in nxt:
+                p[call % 4096::4096] ^= np.uint8(1 + call)
+            payloads = nxt
+
+
 def test_lzo_compress_host(torch_cuda, comp):
     payloads = [payload(k, 70000 + 4099 * i, 400 + i) for i, k in enumerate(KINDS)] + [np.zeros(0, np.uint8)]
     _check(payloads, comp.compress_host([p.tobytes() for p in payloads]))

@@ -24,7 +24,7 @@ EXPORTS = ["zc_create", "zc_destroy", "zc_seed_index", "zc_get_input_buffer",
            "zc_lzo_frame_info", "zc_bundle_scatter", "zc_parse_instructions",
            "zc_aes128_cbc_encrypt", "zc_aes128_cbc_decrypt", "zc_aes128_cbc_encrypt_host",
            "zc_aes128_cbc_decrypt_host", "zc_bundle_file_size", "zc_bundle_seal", "zc_bundle_seal_host",
-           "zc_bundle_unseal", "zc_bundle_unseal_host", "zc_aes_last_form",
+           "zc_bundle_unseal", "zc_bundle_unseal_host", "zc_aes_last_form", "zc_last_stream_paths",
            "zc_gc_plan", "zc_gc_last_stats", "zc_gc_last_times",
            "zc_chunk_meta_compute", "zc_chunk_meta_compute_host", "zc_meta_last_stats"]
 ZC_META_BAD_SHA1, ZC_META_BAD_ROLLING, ZC_META_BAD_SIZE = 1, 2, 4
@@ -33,6 +33,7 @@ ZC_GC_ACT_KEEP, ZC_GC_ACT_REMOVE, ZC_GC_ACT_REPACK, ZC_GC_ACT_DROP_RECORD = 0, 1
 ZC_GC_REC_COUNTED, ZC_GC_REC_USED, ZC_GC_REC_COPIED = 1, 2, 4
 ZC_AES_FORM_DECRYPT, ZC_AES_FORM_PLAIN_TABLES, ZC_AES_FORM_LANE, ZC_AES_FORM_AHEAD_1 = 1, 2, 4, 8
 ZC_AES_FORM_CPW_SHIFT = 8
+ZC_PATH_FUSED_INSERT, ZC_PATH_SCAN_KEYS, ZC_PATH_TABLES_REALLOCATED, ZC_PATH_TABLES_CLEARED_BY_EPOCH = 1, 2, 4, 8
 ZC_BUNDLE_OK, ZC_BUNDLE_BAD_SIZE, ZC_BUNDLE_TRUNCATED = 0, 1, 2
 ZC_BUNDLE_BAD_ADLER1, ZC_BUNDLE_BAD_ADLER2, ZC_BUNDLE_BAD_PADDING = 3, 4, 5
 BUNDLE_STATUS_NAMES = {0: "ok", 1: "bad file size", 2: "truncated", 3: "Adler-32 mismatch after BundleInfo",
@@ -148,6 +149,7 @@ def load(path=LIB_PATH):
         "zc_record_count": (sz, [vp]),
         "zc_get_records": (i32, [vp, ctypes.POINTER(ZcRecord), sz, ctypes.POINTER(sz)]),
         "zc_get_stats": (i32, [vp, ctypes.POINTER(ZcStats)]),
+        "zc_last_stream_paths": (i32, [vp, ctypes.POINTER(u32)]),
         "zc_reset": (i32, [vp]),
         "zc_last_error": (ctypes.c_char_p, [vp]),
         "zc_fill_splitmix64": (i32, [vp, u64, u64, i32]),

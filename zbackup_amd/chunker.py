@@ -266,6 +266,11 @@ class BackupCreator:
     def window(self):
         return int(self._L.zc_get_window(self._ctx))
 
+    def set_window(self, window):
+        """zc_set_window between streams (after reset(), before the next stream's
+        first byte): the feed window in bytes, 0 for the whole stream in HBM."""
+        _check(self._L, self._ctx, self._L.zc_set_window(self._ctx, int(window)), "zc_set_window")
+
     def record_tuples(self):
         """(kind_char, offset, size, rolling, sha1_hex) -- the oracle's format."""
         return [(KIND_CHAR[r["kind"]], int(r["offset"]), int(r["size"]), int(r["rolling"]),
@@ -295,6 +300,14 @@ class BackupCreator:
         st = _lib.ZcStats()
         _check(self._L, self._ctx, self._L.zc_get_stats(self._ctx, ctypes.byref(st)), "zc_get_stats")
         return {name: getattr(st, name) for name, _ in _lib.ZcStats._fields_}
+
+    def last_paths(self):
+        """zc_last_stream_paths: the ZC_PATH_* bits of the last stream this
+        context finished.  Raises ZcError before it has finished one."""
+        bits = ctypes.c_uint32()
+        _check(self._L, self._ctx, self._L.zc_last_stream_paths(self._ctx, ctypes.byref(bits)),
+               "zc_last_stream_paths")
+        return bits.value
 
     def scan_ms(self):
         """zc_stats.scan_ms of the last stream, without building the stats dict

@@ -322,6 +322,11 @@ struct EpochIndex {
   // does the index inserts (no separate clear, no zc_index_insert launch)
   bool tables_clean = false;
 };
+// the form launch_epoch_index takes -- fused: the tables are empty and every
+// key is in (the scan wrote them)
+inline bool epoch_index_fused(const EpochIndex& ix, uint32_t nconf, uint32_t nsref) {
+  return ix.tables_clean && nconf == 0 && nsref && ix.key_from == nsref;
+}
 hipError_t launch_epoch_index(const uint8_t* data, uint64_t n, const uint64_t* blk, AnchorView av, uint64_t r_e,
                               uint32_t nconf, uint32_t nsref, uint32_t W, uint64_t pw, const EpochIndex& ix,
                               hipStream_t s,

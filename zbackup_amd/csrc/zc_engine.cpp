@@ -90,8 +90,10 @@ struct DevBuf {
     p = nullptr;
     cap = 0;
   }
-  void ensure(size_t n) {
-    if (n <= cap && p) return;
+  // room for n elements; true: newly allocated, so whatever the buffer held
+  // is gone (the new one may sit at the old address: the pointer does not tell)
+  bool ensure(size_t n) {
+    if (n <= cap && p) return false;
     release();
     size_t want = n ? n : 1;
     hipError_t e = hipMalloc(&p, want * sizeof(T));
@@ -101,6 +103,7 @@ struct DevBuf {
                                       "): " + hipGetErrorString(e)};
     }
     cap = want;
+    return true;
   }
   // grow to at least n elements (doubling), keeping the first `keep`
   void grow_keep(size_t n, size_t keep, hipStream_t s) {
@@ -508,6 +511,10 @@ struct zc_ctx {
   // the epoch tables (ckeys, tab, gfilt) are empty: cleared at the end of the
   // last stream; the next first epoch inserts without clearing (fused)
   bool tables_clean = false;
+  // ZC_PATH_* bits (zc_last_stream_paths): of the stream in progress, cleared
+  // where a stream starts; and of the last stream finished
+  uint32_t paths = 0, paths_last = 0;
+  bool paths_valid = false;
   HostBuf<unsigned long long> h_co_hc;
   HostBuf<Cand> h_hist_cand;  // the historic candidates, key-checked and in position order
   HostBuf<uint32_t> h_cls;  // the epoch's content classes (likewise)
@@ -756,12 +763,16 @@ void hist_reserve(zc_ctx& c, uint64_t total) {
 uint32_t anchor_def_of(uint32_t W) { return 0x5A410000u | (2u << 8) | (uint32_t)__builtin_ctz(anchor_rate_inv(W)); }
 
 // a by-value entry unless (key, SHA-1) is indexed already (registerNewChunkId,
-// chunk_index.cc:163-182)
+// chunk_index.cc:163-182); an id seeded after one of the context's streams
+// added it is a seeded entry from then on (zc_forget_stream_chunks keeps it)
 void add_static_once(zc_ctx& c, uint64_t key, const uint8_t* sha, uint8_t seeded) {
   auto it = c.smap.find(key);
   if (it != c.smap.end())
     for (uint32_t i : it->second)
-      if (memcmp(c.statics[i].sha, sha, 16) == 0) return;
+      if (memcmp(c.statics[i].sha, sha, 16) == 0) {
+        c.statics[i].seeded |= seeded;
+        return;
+      }
   add_static(c, key, sha, seeded);
 }
 
@@ -1457,12 +1468,12 @@ class Resolver {
       // probe 69 -> 59 us; an eighth saves no more than its larger clear costs)
       uint32_t tbits = 10;
       while ((1u << tbits) < 4u * nref_) ++tbits;
-      const void* const tabs0[3] = {c_.tab.p, c_.gfilt.p, c_.ckeys.p};
+      bool tabs_new = false;  // an epoch table was reallocated: it holds anything
       if (anchors) {
         c_.cand.ensure(std::max<uint64_t>(1u << 16, nref_));
         if (nref_) {
-          c_.tab.ensure(2u << tbits);
-          c_.gfilt.ensure(probe_filter_words());
+          tabs_new |= c_.tab.ensure(2u << tbits);
+          tabs_new |= c_.gfilt.ensure(probe_filter_words());
         }
       }
       c_.h_cnt.ensure(CNT_LAST);
@@ -1492,8 +1503,11 @@ class Resolver {
           HCK(hipMemsetAsync(c_.c_dead.p, 0, nconf_, c_.stream));
         }
         // content classes: identical refs share one leader in the table
-        c_.ckeys.ensure(1u << tbits);
-        if (c_.tab.p != tabs0[0] || c_.gfilt.p != tabs0[1] || c_.ckeys.p != tabs0[2]) c_.tables_clean = false;
+        tabs_new |= c_.ckeys.ensure(1u << tbits);
+        if (tabs_new) {
+          c_.tables_clean = false;
+          c_.paths |= ZC_PATH_TABLES_REALLOCATED;
+        }
         c_.c_cls.ensure(nref_);
         c_.cpairs.ensure(nref_);
         ix = EpochIndex{c_.c_start.p, c_.c_vis.p, c_.c_dead.p, c_.c_key.p,
@@ -1504,6 +1518,8 @@ class Resolver {
         ix.key_from = key_from;
         ix.tables_clean = c_.tables_clean;
         c_.tables_clean = false;  // this epoch fills them
+        if (key_from) c_.paths |= ZC_PATH_SCAN_KEYS;
+        c_.paths |= epoch_index_fused(ix, nconf_, nsref) ? ZC_PATH_FUSED_INSERT : ZC_PATH_TABLES_CLEARED_BY_EPOCH;
         if (scnt_pending_) {  // the chunk-metadata kernel hands the scan's counters over
           ix.scnt = c_.scnt.p;
           ix.h_scnt = c_.h_scnt.p;
@@ -3152,6 +3168,7 @@ void window_open(zc_ctx& c) {
   c.hwin.ensure(c.win_cap);
   c.wbase = c.wend = 0;
   c.windowed_last = true;
+  c.paths = 0;
   c.res = new Resolver(c, c.dwin.p, 0, true);
   c.res->begin();
 }
@@ -3217,6 +3234,14 @@ void window_add(zc_ctx& c, size_t added) {
     c.res->run_segment(c.wend / ZC_STILE * ZC_STILE);
     c.slide_pending = true;
   }
+}
+
+// a stream's last call has returned its records: its path bits are the ones
+// zc_last_stream_paths reports from now on
+void stream_done(zc_ctx& c) {
+  c.finished = true;
+  c.paths_last = c.paths;
+  c.paths_valid = true;
 }
 
 size_t ctx_hbm_bytes(const zc_ctx& c) {
@@ -3541,17 +3566,18 @@ int zc_finish(zc_ctx* c) {
       window_close(*c);
       c->d_last = c->dwin.p;
       c->n_last = c->wend;
-      c->finished = true;
+      stream_done(*c);
     });
   }
   return guarded(c, [&] {
     DeviceGuard g(c->device);
     c->windowed_last = false;
+    c->paths = 0;
     Resolver res(*c, c->d_stream.p, c->n_stream, false);
     res.run();
     c->d_last = c->d_stream.p;
     c->n_last = c->n_stream;
-    c->finished = true;
+    stream_done(*c);
   });
 }
 
@@ -3572,6 +3598,7 @@ int zc_chunk_device(zc_ctx* c, const void* d_data, uint64_t n) {
       HCK(hipStreamWaitEvent(c->stream, c->ev_in, 0));
     }
     c->windowed_last = false;
+    c->paths = 0;
     const uint32_t nh = c->nhist;
     const size_t ns = c->statics.size();
     bool redo = false;
@@ -3593,7 +3620,7 @@ int zc_chunk_device(zc_ctx* c, const void* d_data, uint64_t n) {
     }
     c->d_last = (const uint8_t*)d_data;
     c->n_last = n;
-    c->finished = true;
+    stream_done(*c);
   });
 }
 
@@ -3609,6 +3636,7 @@ int zc_chunk_host(zc_ctx* c, const void* host, uint64_t n) {
     }
     c->n_stream = n;
     c->windowed_last = false;
+    c->paths = 0;
     uint8_t* d = c->d_stream.p;
     const uint8_t* h = (const uint8_t*)host;
     // segments land on the copy stream; the scan of each follows on the
@@ -3625,7 +3653,7 @@ int zc_chunk_host(zc_ctx* c, const void* host, uint64_t n) {
     res.run_final();
     c->d_last = d;
     c->n_last = n;
-    c->finished = true;
+    stream_done(*c);
   });
 }
 
@@ -3673,6 +3701,19 @@ int zc_get_stats(const zc_ctx* c, zc_stats* out) {
   out->hist_seeded = c->nhist_seeded;
   out->by_value = c->statics.size();
   out->window_bytes = c->win_cap;
+  return ZC_OK;
+}
+
+int zc_last_stream_paths(const zc_ctx* cc, uint32_t* bits) {
+  zc_ctx* c = const_cast<zc_ctx*>(cc);  // the message is the context's
+  ZC_LOCK(c);
+  if (!c || !bits) return ZC_ERR_ARG;
+  if (!c->paths_valid) {
+    c->err = "zc_last_stream_paths: this context has finished no stream yet";
+    return ZC_ERR_STATE;
+  }
+  *bits = c->paths_last;
+  c->err.clear();
   return ZC_OK;
 }
 

@@ -3093,8 +3093,7 @@ hipError_t launch_epoch_index(const uint8_t* data, uint64_t n, const uint64_t* b
                               uint32_t nconf, uint32_t nsref, uint32_t W, uint64_t pw, const EpochIndex& ix,
                               hipStream_t s, hipEvent_t after_meta) {
   const uint32_t nref = nconf + nsref;
-  // fused: the tables are empty and every key is in (the scan wrote them)
-  const bool fused = ix.tables_clean && nconf == 0 && nsref && ix.key_from == nsref;
+  const bool fused = epoch_index_fused(ix, nconf, nsref);
   const EpochClear ec{ix.ckeys, nref && !fused ? 1u << ix.cbits : 0u, ix.tab,
                       ix.tab && !fused ? 2ull << ix.tbits : 0ull, ix.gfilt, ix.tab && !fused ? kGFiltWords : 0u,
                       ix.counters, ix.scnt, ix.h_scnt};

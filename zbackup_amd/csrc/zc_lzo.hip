@@ -263,12 +263,21 @@ struct LzoScratch {
   Buf<Copy> copies;
   Buf<uint64_t> out_size, or_at;
   Buf<uint32_t> or_val;
+  uint32_t gen0 = 0;  // the generation fresh dictionaries start from (0; tests: ZC_TEST_LZO_GEN0)
   uint32_t gen = 0;  // tag of the dictionaries' live entries
   hipEvent_t e0 = nullptr, e1 = nullptr;
   LzoTimes times{};
 };
 
-LzoScratch* lzo_scratch_new() { return new LzoScratch(); }
+LzoScratch* lzo_scratch_new() {
+  LzoScratch* s = new LzoScratch();
+  // (ZC_TEST_LZO_GEN0: tests start the 16-bit generation near its wrap, which
+  // a context otherwise reaches after 65,535 batches; used only inside [0, 0xffff])
+  const char* tg = getenv("ZC_TEST_LZO_GEN0");
+  const long tgv = tg ? strtol(tg, nullptr, 10) : 0;
+  if (tgv >= 0 && tgv <= 0xffff) s->gen = s->gen0 = (uint32_t)tgv;
+  return s;
+}
 void lzo_scratch_free(LzoScratch* s) {
   if (!s) return;
   if (s->e0) (void)hipEventDestroy(s->e0);
@@ -350,9 +359,10 @@ static hipError_t lzo_batch(LzoScratch* s, const uint8_t* d_payload, const uint6
   // context's streams are non-blocking, so a null-stream memset would not be)
   bool fresh = false;
   LCK(s->dict.ensure((size_t)nblk * kDictSize, &fresh));
+  if (fresh) s->gen = s->gen0;
   if (fresh || s->gen == 0xffff) {
     LCK(hipMemsetAsync(s->dict.p, 0, s->dict.cap * sizeof(uint32_t), st));
-    s->gen = 0;
+    if (s->gen == 0xffff) s->gen = 0;
   }
   const uint32_t tag = ++s->gen;
   LCK(s->stage.ensure((size_t)nblk * kStageCap));
