@@ -51,6 +51,8 @@
  *   zc_chunk_meta_compute  no counterpart: the metadata of zc_export_chunk_meta and the full
  *                          ChunkId (chunk_id.hh:16-32, made at backup_creator.cc:127-141) of chunks
  *                          read back out of decoded bundles (Bundle::Reader::get, bundle.cc:235-251)
+ *   zc_range_read          BackupRestorer::IndexedRestorer::saveData, a batch of ranges per call
+ *                          (zc_range_index_create: its constructor)     backup_restorer.cc:182-316
  *   zc_last_error          the DEF_EX exceptions / CHECK aborts of the reference
  *                          (backup_creator.cc:112,165-166, chunk_index.hh:88-89)
  */
@@ -583,6 +585,53 @@ int zc_chunk_meta_compute_host(zc_ctx* ctx, const void* payload, uint64_t payloa
 /* The context's last such call: device time of the rolling-hash / anchor kernel and of the SHA-1
  * kernel, and the whole call's wall clock (uploads, both read-backs and the wait included). */
 int zc_meta_last_stats(const zc_ctx* ctx, double* meta_ms, double* sha1_ms, double* total_ms);
+
+/* ---- Random-access restore: any byte range of a backup, from resident bundle payloads ----
+ * BackupRestorer::IndexedRestorer (backup_restorer.cc:182-316), which `zbackup nbd` serves a
+ * backup through.  The index is made from the stream's entries -- each chunk_to_emit and each
+ * bytes_to_emit, in stream order --: entry e is sizes[e] bytes at off[e] of slot[e].  A slot is one
+ * resident payload of a size fixed here: a bundle's decoded payload, or the instruction stream
+ * itself for the bytes_to_emit runs.  Creation computes the entries' stream positions (the
+ * running sum) and checks every entry; ZC_ERR_ARG with a message naming the entry when it names
+ * no slot, ends past its slot's size, or takes the sum past 2^64.  ctx gives the device the
+ * index's arrays are uploaded to, once; with ctx NULL the index is host only (total, needs and
+ * every check work) until the first zc_range_read brings a context.  The index holds no stream
+ * state: one context may serve many indices.  Callers detect these entry points by their symbols
+ * (the ABI version stays 5). */
+typedef struct zc_range_index zc_range_index;
+int zc_range_index_create(zc_ctx* ctx, const uint64_t* slot_sizes, size_t n_slots, const uint32_t* slot,
+                          const uint64_t* off, const uint64_t* sizes, size_t n, zc_range_index** idx);
+int zc_range_index_total(const zc_range_index* idx, uint64_t* bytes);
+int zc_range_index_destroy(zc_range_index* idx);
+/* A slot's payload: caller-owned device memory of the slot's size (NULL clears it), or a copy the
+ * index makes of host bytes and owns (size must equal the slot's); drop clears either.  A pointer
+ * may be set, replaced or cleared at any time between calls, so a caller with a bundle cache keeps
+ * only part of a large backup in HBM. */
+int zc_range_set_slot(zc_range_index* idx, uint32_t slot, const void* d_ptr);
+int zc_range_slot_upload(zc_range_index* idx, uint32_t slot, const void* host, uint64_t size);
+int zc_range_slot_drop(zc_range_index* idx, uint32_t slot);
+/* Host only: the distinct slots the reads [offset[i], offset[i] + size[i]) touch, ascending, into
+ * slots_out (room for cap); *n_out receives their number, also when cap is too small (ZC_ERR_ARG). */
+int zc_range_needs(const zc_range_index* idx, const uint64_t* offset, const uint64_t* size, size_t n_reads,
+                   uint32_t* slots_out, size_t cap, size_t* n_out);
+/* One batch of reads: read i's bytes go to d_dst + dst_off[i] (any alignment; destinations must
+ * not overlap).  Checked on the host before any device work, ZC_ERR_ARG with a message and nothing
+ * written: offset + size > total or wrapping (the reference's exOutOfRange; 0 bytes at offset ==
+ * total is allowed, as there); a touched slot without a pointer (the message names the slot); a
+ * NULL argument with n_reads > 0.  The reads are cut into pieces of at most 64 KiB, one wave
+ * each; every wave checks each source range against its slot's size again (ZC_ERR_STATE if one
+ * fails: an internal error). */
+int zc_range_read(zc_ctx* ctx, zc_range_index* idx, const uint64_t* offset, const uint64_t* size, size_t n_reads,
+                  void* d_dst, const uint64_t* dst_off);
+/* Both forms run on the context's stream after the work the caller has queued on the default
+ * stream so far, as the other bundle calls do: slots just filled there (a copy, a decode kernel)
+ * are read as filled.  Work on other streams is the caller's to finish first.
+ * The same to host memory, through a pinned staging buffer of the context: */
+int zc_range_read_host(zc_ctx* ctx, zc_range_index* idx, const uint64_t* offset, const uint64_t* size,
+                       size_t n_reads, void* host_dst, const uint64_t* dst_off);
+/* The context's last such call: device time of the piece list's upload and of the kernel, and
+ * the number of pieces. */
+int zc_range_last_stats(const zc_ctx* ctx, double* upload_ms, double* kernel_ms, uint64_t* pieces);
 
 int zc_abi_version(void);
 /* digest of the sources this library was built from (zbackup_amd/_build.py

@@ -37,6 +37,7 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include <map>
 #include <mutex>
 #include <stdexcept>
 #include <string>
@@ -773,6 +774,212 @@ public:
 
   uint64_t chunksSeen() const { return chunks; }
   uint64_t bytesSeen() const { return bytes; }
+};
+
+/// BackupRestorer::IndexedRestorer (backup_restorer.cc:182-316, backup_restorer.hh:55-79)
+/// on the GPU: size() and saveData( offset, data, size ) with the reference's
+/// signatures, so `zbackup nbd` (zutils.cc:262-297) can serve a backup from it.
+/// Built from the backup data, every bundle's ( chunk id blob, size ) list --
+/// what Bundle::Reader reads from BundleInfo (bundle.cc:220-232) -- and a source
+/// that hands over a bundle's decoded payload on demand.  The payloads a read
+/// touches are made resident in HBM (zc_range_needs, zc_range_slot_upload); the
+/// least recently used ones leave when the resident bytes pass `budget`.  The
+/// bundles of the read being served are always admitted, so the budget bounds
+/// what stays between reads; a long read is served in steps of StepBytes to
+/// keep one step's bundles few.  Uses the C ABI only.
+class GpuIndexedRestorer: NoCopy
+{
+public:
+  typedef std::vector< std::pair< std::string, uint32_t > > ChunkList;  // one bundle: ( ChunkId blob, size ) in order
+
+  /// Bundle::Reader for bundle number `bundle` of the list given: all of its chunks, back to back
+  struct PayloadSource
+  {
+    virtual void getPayload( size_t bundle, std::string & payload ) = 0;
+    virtual ~PayloadSource() {}
+  };
+
+  struct exOutOfRange: std::runtime_error
+  {
+    exOutOfRange(): std::runtime_error( "IndexedRestorer: the range is outside the backup" ) {}
+  };
+
+  enum { StepBytes = 4 << 20 };
+
+private:
+  struct Where
+  {
+    uint32_t bundle;
+    uint64_t off;
+    uint32_t size;
+  };
+
+  zc_ctx * ctx;
+  zc_range_index * index;
+  PayloadSource & source;
+  uint64_t budget;
+  int64_t totalSize;
+  std::vector< size_t > bundleOfSlot;  // slot -> bundle number
+  std::vector< uint64_t > slotSize;
+  // the cache of resident payloads: saveData is const, as the reference's
+  mutable uint64_t residentBytes, tick, fetches, evictions;
+  mutable std::vector< uint64_t > lastUse;
+  mutable std::vector< char > resident;
+
+  static void check( int rc, char const * what )
+  {
+    if ( rc != ZC_OK )
+      throw std::runtime_error( std::string( what ) + ": " + zc_last_error( 0 ) );
+  }
+
+  void evictDownTo( uint64_t room, std::vector< char > const & wanted ) const
+  {
+    while ( residentBytes > room )
+    {
+      size_t victim = resident.size();
+      for ( size_t s = 0; s < resident.size(); ++s )
+        if ( resident[ s ] && !wanted[ s ] && ( victim == resident.size() || lastUse[ s ] < lastUse[ victim ] ) )
+          victim = s;
+      if ( victim == resident.size() )
+        return;  // only this read's own bundles are left
+      check( zc_range_slot_drop( index, (uint32_t)victim ), "zc_range_slot_drop" );
+      resident[ victim ] = 0;
+      residentBytes -= slotSize[ victim ];
+      ++evictions;
+    }
+  }
+
+  void step( uint64_t offset, char * data, uint64_t size ) const
+  {
+    std::vector< uint32_t > slots( slotSize.size() + 1 );  // ascending
+    size_t n = 0;
+    check( zc_range_needs( index, &offset, &size, 1, slots.data(), slots.size(), &n ), "zc_range_needs" );
+    if ( n && slots[ n - 1 ] == slotSize.size() )
+      --n;  // the instruction stream's slot (the last): always resident, outside the budget
+    std::vector< char > wanted( resident.size(), 0 );
+    uint64_t missing = 0;
+    for ( size_t i = 0; i < n; ++i )
+    {
+      wanted[ slots[ i ] ] = 1;
+      lastUse[ slots[ i ] ] = ++tick;
+      if ( !resident[ slots[ i ] ] )
+        missing += slotSize[ slots[ i ] ];
+    }
+    evictDownTo( budget > missing ? budget - missing : 0, wanted );
+    std::string payload;
+    for ( size_t i = 0; i < n; ++i )
+    {
+      uint32_t s = slots[ i ];
+      if ( resident[ s ] )
+        continue;
+      source.getPayload( bundleOfSlot[ s ], payload );
+      if ( payload.size() != slotSize[ s ] )
+        throw std::runtime_error( "IndexedRestorer: a bundle's payload is not the sum of its chunk sizes" );
+      check( zc_range_slot_upload( index, s, payload.data(), payload.size() ), "zc_range_slot_upload" );
+      resident[ s ] = 1;
+      residentBytes += slotSize[ s ];
+      ++fetches;
+    }
+    uint64_t at = 0;
+    zcCheck( zc_range_read_host( ctx, index, &offset, &size, 1, data, &at ), ctx, "zc_range_read_host" );
+  }
+
+public:
+  GpuIndexedRestorer( std::string const & backupData, std::vector< ChunkList > const & bundles,
+                      PayloadSource & source, uint64_t budget, int device = 0 ):
+    ctx( 0 ), index( 0 ), source( source ), budget( budget ), totalSize( 0 ), residentBytes( 0 ), tick( 0 ),
+    fetches( 0 ), evictions( 0 )
+  {
+    // Bundle::Reader::Reader's id -> chunk map, per bundle; an id in two bundles keeps the first
+    std::map< std::string, Where > ids;
+    std::vector< uint64_t > payloadSize( bundles.size(), 0 );
+    for ( size_t b = 0; b < bundles.size(); ++b )
+      for ( size_t i = 0; i < bundles[ b ].size(); ++i )
+      {
+        if ( bundles[ b ][ i ].first.size() != 24 )
+          throw std::runtime_error( "IndexedRestorer: a chunk id that is not 24 bytes" );
+        Where w = { (uint32_t)b, payloadSize[ b ], bundles[ b ][ i ].second };
+        ids.insert( std::make_pair( bundles[ b ][ i ].first, w ) );
+        payloadSize[ b ] += bundles[ b ][ i ].second;
+      }
+    // a count pass first (no room given: the call reports the entries it found), so the list
+    // takes what the stream holds and not the two-bytes-per-entry worst case
+    size_t count = 0;
+    zc_parse_instructions( backupData.data(), backupData.size(), 0, 0, &count );
+    std::vector< zc_instruction > ins( count + 1 );
+    check( zc_parse_instructions( backupData.data(), backupData.size(), ins.data(), ins.size(), &count ),
+           "zc_parse_instructions" );
+    // slots: the bundles the stream names, in first-use order, then the instruction stream
+    std::map< size_t, uint32_t > slotOfBundle;
+    std::vector< uint32_t > slot( count );
+    std::vector< uint64_t > off( count ), size( count );
+    for ( size_t e = 0; e < count; ++e )
+      if ( ins[ e ].kind == ZC_INSTR_CHUNK )
+      {
+        std::map< std::string, Where >::const_iterator it = ids.find( std::string( (char const *)ins[ e ].id, 24 ) );
+        if ( it == ids.end() )
+          throw std::runtime_error( "IndexedRestorer: the backup names a chunk no bundle holds" );
+        std::map< size_t, uint32_t >::const_iterator known = slotOfBundle.find( it->second.bundle );
+        if ( known == slotOfBundle.end() )
+        {
+          known = slotOfBundle.insert( std::make_pair( (size_t)it->second.bundle, (uint32_t)bundleOfSlot.size() ) ).first;
+          bundleOfSlot.push_back( it->second.bundle );
+          slotSize.push_back( payloadSize[ it->second.bundle ] );
+        }
+        slot[ e ] = known->second;
+        off[ e ] = it->second.off;
+        size[ e ] = it->second.size;
+      }
+    uint32_t instrSlot = (uint32_t)slotSize.size();
+    for ( size_t e = 0; e < count; ++e )
+      if ( ins[ e ].kind != ZC_INSTR_CHUNK )
+      {
+        slot[ e ] = instrSlot;
+        off[ e ] = ins[ e ].data_off;
+        size[ e ] = ins[ e ].size;
+      }
+    slotSize.push_back( backupData.size() );
+    zcCheck( zc_create( &ctx, 65536, device, 0 ), 0, "zc_create" );
+    int rc = zc_range_index_create( ctx, slotSize.data(), slotSize.size(), slot.data(), off.data(), size.data(),
+                                    count, &index );
+    uint64_t total = 0;
+    if ( rc == ZC_OK )
+      rc = zc_range_index_total( index, &total );
+    if ( rc == ZC_OK )
+      rc = zc_range_slot_upload( index, instrSlot, backupData.data(), backupData.size() );
+    if ( rc != ZC_OK || total > (uint64_t)INT64_MAX )
+    {
+      std::string err = rc != ZC_OK ? std::string( zc_last_error( index ? 0 : ctx ) ) : "the backup is 2^63 bytes or more";
+      if ( index )
+        zc_range_index_destroy( index );
+      zc_destroy( ctx );
+      throw std::runtime_error( "IndexedRestorer: " + err );
+    }
+    totalSize = (int64_t)total;
+    slotSize.pop_back();  // the instruction stream stays resident and outside the budget
+    resident.assign( slotSize.size(), 0 );
+    lastUse.assign( slotSize.size(), 0 );
+  }
+
+  ~GpuIndexedRestorer()
+  {
+    zc_range_index_destroy( index );
+    zc_destroy( ctx );
+  }
+
+  int64_t size() const { return totalSize; }
+
+  void saveData( int64_t offset, void * data, size_t size ) const
+  {
+    if ( offset < 0 || (uint64_t)size > (uint64_t)totalSize || (uint64_t)offset > (uint64_t)totalSize - size )
+      throw exOutOfRange();
+    for ( uint64_t k = 0; k < size; k += StepBytes )
+      step( (uint64_t)offset + k, (char *)data + k, size - k < (uint64_t)StepBytes ? size - k : (uint64_t)StepBytes );
+  }
+
+  uint64_t residentPayloadBytes() const { return residentBytes; }
+  uint64_t payloadsFetched() const { return fetches; }
+  uint64_t payloadsEvicted() const { return evictions; }
 };
 
 #endif

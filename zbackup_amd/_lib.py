@@ -26,7 +26,10 @@ EXPORTS = ["zc_create", "zc_destroy", "zc_seed_index", "zc_get_input_buffer",
            "zc_aes128_cbc_decrypt_host", "zc_bundle_file_size", "zc_bundle_seal", "zc_bundle_seal_host",
            "zc_bundle_unseal", "zc_bundle_unseal_host", "zc_aes_last_form", "zc_last_stream_paths",
            "zc_gc_plan", "zc_gc_last_stats", "zc_gc_last_times",
-           "zc_chunk_meta_compute", "zc_chunk_meta_compute_host", "zc_meta_last_stats"]
+           "zc_chunk_meta_compute", "zc_chunk_meta_compute_host", "zc_meta_last_stats",
+           "zc_range_index_create", "zc_range_index_total", "zc_range_index_destroy", "zc_range_set_slot",
+           "zc_range_slot_upload", "zc_range_slot_drop", "zc_range_needs", "zc_range_read", "zc_range_read_host",
+           "zc_range_last_stats"]
 ZC_META_BAD_SHA1, ZC_META_BAD_ROLLING, ZC_META_BAD_SIZE = 1, 2, 4
 ZC_GC_DEEP, ZC_GC_REPACK, ZC_GC_CONCAT = 1, 2, 4
 ZC_GC_ACT_KEEP, ZC_GC_ACT_REMOVE, ZC_GC_ACT_REPACK, ZC_GC_ACT_DROP_RECORD = 0, 1, 2, 3
@@ -205,6 +208,20 @@ def load(path=LIB_PATH):
         "zc_chunk_meta_compute": (i32, [vp, vp, u64, vp, vp, sz, vp, vp, vp, ctypes.POINTER(sz)]),
         "zc_chunk_meta_compute_host": (i32, [vp, vp, u64, vp, vp, sz, vp, vp, vp, ctypes.POINTER(sz)]),
         "zc_meta_last_stats": (i32, [vp] + [ctypes.POINTER(ctypes.c_double)] * 3),
+        # random-access restore: (ctx, slot_sizes, n_slots, slot, off, sizes, n, &idx)
+        "zc_range_index_create": (i32, [vp, vp, sz, vp, vp, vp, sz, ctypes.POINTER(vp)]),
+        "zc_range_index_total": (i32, [vp, ctypes.POINTER(u64)]),
+        "zc_range_index_destroy": (i32, [vp]),
+        "zc_range_set_slot": (i32, [vp, u32, vp]),
+        "zc_range_slot_upload": (i32, [vp, u32, vp, u64]),
+        "zc_range_slot_drop": (i32, [vp, u32]),
+        # (idx, offset, size, n_reads, slots_out, cap, &n_out)
+        "zc_range_needs": (i32, [vp, vp, vp, sz, vp, sz, ctypes.POINTER(sz)]),
+        # (ctx, idx, offset, size, n_reads, dst, dst_off)
+        "zc_range_read": (i32, [vp, vp, vp, vp, sz, vp, vp]),
+        "zc_range_read_host": (i32, [vp, vp, vp, vp, sz, vp, vp]),
+        "zc_range_last_stats": (i32, [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                      ctypes.POINTER(u64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

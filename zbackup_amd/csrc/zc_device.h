@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <mutex>
 #include <string>
 
 #include "../../include/zchunk.h"  // zc_seed, zc_chunk_meta (typedefs of unnamed structs)
@@ -562,5 +563,36 @@ int meta_validate(const void* payload, uint64_t payload_bytes, const uint64_t* o
 int meta_compute(MetaScratch* s, bool host, const void* payload, uint64_t payload_bytes, const uint64_t* off,
                  const uint32_t* size, size_t n, uint32_t W, uint32_t def, const zc_seed* expect, zc_chunk_meta* out,
                  uint8_t* status, size_t* n_bad, hipEvent_t ev_in, hipStream_t st, std::string& err);
+
+// zc_range.hip: random-access restore (zc_range_core.h).  What the host can
+// see is checked by range_index_create / range_validate_read / range_needs with
+// no device and no context; each returns a zc_status with its message in `err`.
+struct RangeScratch;
+struct RangeTimes {
+  double upload_ms, kernel_ms;  // the piece list's copy and the kernel, summed over the call's launches
+  uint64_t pieces;
+};
+RangeScratch* range_scratch_new();
+void range_scratch_free(RangeScratch* s);
+const RangeTimes* range_times(const RangeScratch* s);
+int range_index_create(const uint64_t* slot_sizes, size_t n_slots, const uint32_t* slot, const uint64_t* off,
+                       const uint64_t* sizes, size_t n, zc_range_index** out, std::string& err);
+// range_index_attach, range_validate_read and range_read want range_mutex held by the caller, who
+// keeps it from the check to the end of the read: the slot table stays as checked until the kernel is done
+std::mutex& range_mutex(zc_range_index* ix);
+int range_index_attach(zc_range_index* ix, int device, hipStream_t st, std::string& err);
+void range_index_destroy(zc_range_index* ix);
+uint64_t range_index_total(const zc_range_index* ix);
+int range_set_slot(zc_range_index* ix, uint32_t slot, const void* d_ptr, std::string& err);
+int range_slot_upload(zc_range_index* ix, uint32_t slot, const void* host, uint64_t size, std::string& err);
+int range_slot_drop(zc_range_index* ix, uint32_t slot, std::string& err);
+int range_needs(const zc_range_index* ix, const uint64_t* offset, const uint64_t* size, size_t n_reads,
+                uint32_t* slots_out, size_t cap, size_t* n_out, std::string& err);
+int range_validate_read(zc_range_index* ix, const uint64_t* offset, const uint64_t* size, size_t n_reads,
+                        const void* dst, const uint64_t* dst_off, std::string& err);
+// host: dst is host memory (the reads go through a pinned staging buffer);
+// else ev_in orders the context stream after the legacy default stream
+int range_read(RangeScratch* s, zc_range_index* ix, const uint64_t* offset, const uint64_t* size, size_t n_reads,
+               void* dst, const uint64_t* dst_off, bool host, hipEvent_t ev_in, hipStream_t st, std::string& err);
 
 }  // namespace zc

@@ -531,6 +531,7 @@ struct zc_ctx {
   AesScratch* aes = nullptr;  // AES-128-CBC and bundle files (zc_aes.hip), made on first use
   GcScratch* gc = nullptr;    // garbage collection's tables (zc_gc.hip), made on first use
   MetaScratch* meta = nullptr;  // adoption's buffers (zc_meta.hip), made on first use
+  RangeScratch* range = nullptr;  // random-access restore's buffers (zc_range.hip), made on first use
 
   // scratch
   DevBuf<uint64_t> hm_key, hm_fp, hm_rkey;  // metadata of chunks joining the historic index
@@ -3331,6 +3332,7 @@ int zc_destroy(zc_ctx* c) {
     aes_scratch_free(c->aes);
     gc_scratch_free(c->gc);
     meta_scratch_free(c->meta);
+    range_scratch_free(c->range);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     if (prev >= 0) (void)hipSetDevice(prev);
@@ -4312,5 +4314,147 @@ int zc_meta_last_stats(const zc_ctx* c, double* meta_ms, double* sha1_ms, double
   if (meta_ms) *meta_ms = t.meta_ms;
   if (sha1_ms) *sha1_ms = t.sha1_ms;
   if (total_ms) *total_ms = t.total_ms;
+  return ZC_OK;
+}
+
+// ---- random-access restore: the range index and its read kernel (zc_range.hip) ----
+
+int zc_range_index_create(zc_ctx* c, const uint64_t* slot_sizes, size_t n_slots, const uint32_t* slot,
+                          const uint64_t* off, const uint64_t* sizes, size_t n, zc_range_index** idx) {
+  ZC_LOCK(c);
+  std::string err;
+  try {
+    // what the host can see is checked before the context is looked at
+    int rc = range_index_create(slot_sizes, n_slots, slot, off, sizes, n, idx, err);
+    if (rc != ZC_OK) return ctx_arg_error(c, ("zc_range_index_create: " + err).c_str());
+    if (!c) {  // host only until a read brings a context
+      g_host_err.clear();
+      return ZC_OK;
+    }
+    DeviceGuard g(c->device);
+    {
+      std::lock_guard<std::mutex> ilk(range_mutex(*idx));
+      rc = range_index_attach(*idx, c->device, c->stream, err);
+    }
+    if (rc != ZC_OK) {
+      range_index_destroy(*idx);
+      *idx = nullptr;
+      c->err = "zc_range_index_create: " + err;
+      return rc;
+    }
+  } catch (const std::bad_alloc&) {
+    return c ? fail(c, ZcError{ZC_ERR_NOMEM, "host allocation failed"}) : ZC_ERR_NOMEM;
+  }
+  c->err.clear();
+  return ZC_OK;
+}
+
+int zc_range_index_total(const zc_range_index* idx, uint64_t* bytes) {
+  if (!idx || !bytes) return host_arg_error("zc_range_index_total: null pointer");
+  *bytes = range_index_total(idx);
+  return ZC_OK;
+}
+
+int zc_range_index_destroy(zc_range_index* idx) {
+  if (!idx) return host_arg_error("zc_range_index_destroy: null index");
+  range_index_destroy(idx);
+  return ZC_OK;
+}
+
+// the slot calls and zc_range_needs take no context: their message is the
+// thread's (zc_last_error(NULL))
+
+int zc_range_set_slot(zc_range_index* idx, uint32_t slot, const void* d_ptr) {
+  if (!idx) return host_arg_error("zc_range_set_slot: null index");
+  std::string err;
+  const int rc = range_set_slot(idx, slot, d_ptr, err);
+  g_host_err = rc != ZC_OK ? "zc_range_set_slot: " + err : std::string();
+  return rc;
+}
+
+int zc_range_slot_upload(zc_range_index* idx, uint32_t slot, const void* host, uint64_t size) {
+  if (!idx) return host_arg_error("zc_range_slot_upload: null index");
+  std::string err;
+  const int rc = range_slot_upload(idx, slot, host, size, err);
+  g_host_err = rc != ZC_OK ? "zc_range_slot_upload: " + err : std::string();
+  return rc;
+}
+
+int zc_range_slot_drop(zc_range_index* idx, uint32_t slot) {
+  if (!idx) return host_arg_error("zc_range_slot_drop: null index");
+  std::string err;
+  const int rc = range_slot_drop(idx, slot, err);
+  g_host_err = rc != ZC_OK ? "zc_range_slot_drop: " + err : std::string();
+  return rc;
+}
+
+int zc_range_needs(const zc_range_index* idx, const uint64_t* offset, const uint64_t* size, size_t n_reads,
+                   uint32_t* slots_out, size_t cap, size_t* n_out) {
+  if (!idx) return host_arg_error("zc_range_needs: null index");
+  std::string err;
+  int rc;
+  try {
+    rc = range_needs(idx, offset, size, n_reads, slots_out, cap, n_out, err);
+  } catch (const std::bad_alloc&) {
+    g_host_err = "zc_range_needs: host allocation failed";
+    return ZC_ERR_NOMEM;
+  }
+  g_host_err = rc != ZC_OK ? "zc_range_needs: " + err : std::string();
+  return rc;
+}
+
+static int range_read_entry(zc_ctx* c, const char* what, bool host, zc_range_index* idx, const uint64_t* offset,
+                            const uint64_t* size, size_t n_reads, void* dst, const uint64_t* dst_off) {
+  if (!idx) return ctx_arg_error(c, (std::string(what) + ": null index").c_str());
+  std::string err;
+  int rc;
+  // held from the residency check to the end of the read: no slot leaves in between
+  std::lock_guard<std::mutex> ilk(range_mutex(idx));
+  try {
+    // what the host can see is checked before the context is looked at
+    rc = range_validate_read(idx, offset, size, n_reads, dst, dst_off, err);
+    if (rc != ZC_OK) return ctx_arg_error(c, (std::string(what) + ": " + err).c_str());
+    if (!c) return ctx_arg_error(c, (std::string(what) + ": null context").c_str());
+    if (!n_reads) {
+      c->err.clear();
+      return ZC_OK;
+    }
+    DeviceGuard g(c->device);
+    rc = range_index_attach(idx, c->device, c->stream, err);
+    if (rc == ZC_OK) {
+      if (!c->range) c->range = range_scratch_new();
+      rc = range_read(c->range, idx, offset, size, n_reads, dst, dst_off, host, c->ev_in, c->stream, err);
+    }
+  } catch (const ZcError& e) {
+    return fail(c, e);
+  } catch (const std::bad_alloc&) {
+    return c ? fail(c, ZcError{ZC_ERR_NOMEM, "host allocation failed"}) : ZC_ERR_NOMEM;
+  }
+  if (rc != ZC_OK)
+    c->err = std::string(what) + ": " + err;
+  else
+    c->err.clear();
+  return rc;
+}
+
+int zc_range_read(zc_ctx* c, zc_range_index* idx, const uint64_t* offset, const uint64_t* size, size_t n_reads,
+                  void* d_dst, const uint64_t* dst_off) {
+  ZC_LOCK(c);
+  return range_read_entry(c, "zc_range_read", false, idx, offset, size, n_reads, d_dst, dst_off);
+}
+
+int zc_range_read_host(zc_ctx* c, zc_range_index* idx, const uint64_t* offset, const uint64_t* size,
+                       size_t n_reads, void* host_dst, const uint64_t* dst_off) {
+  ZC_LOCK(c);
+  return range_read_entry(c, "zc_range_read_host", true, idx, offset, size, n_reads, host_dst, dst_off);
+}
+
+int zc_range_last_stats(const zc_ctx* c, double* upload_ms, double* kernel_ms, uint64_t* pieces) {
+  ZC_LOCK(c);
+  if (!c) return host_arg_error("zc_range_last_stats: null context");
+  const RangeTimes t = c->range ? *range_times(c->range) : RangeTimes{};
+  if (upload_ms) *upload_ms = t.upload_ms;
+  if (kernel_ms) *kernel_ms = t.kernel_ms;
+  if (pieces) *pieces = t.pieces;
   return ZC_OK;
 }

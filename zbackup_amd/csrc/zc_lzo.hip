@@ -28,6 +28,7 @@
 #include <vector>
 
 #define ZC_HD __host__ __device__
+#include "zc_copy_body.h"
 #include "zc_device.h"
 #include "zc_lzo_core.h"
 
@@ -55,7 +56,7 @@ struct Copy {
   uint64_t n;
 };
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+using zccopy::u32x4;
 
 struct TagDict {
   uint32_t* d;
@@ -107,38 +108,14 @@ __global__ __launch_bounds__(64) void zc_lzo_chain_kernel(const uint8_t* __restr
 
 // one wave per copy: a head of bytes up to the destination's 16-byte
 // alignment, 16-byte aligned stores (the source read unaligned), a byte tail
+// (zc_copy_body.h, shared with the range read)
 __global__ __launch_bounds__(256) void zc_lzo_copy_kernel(const Copy* __restrict__ copies, uint32_t n) {
   const uint32_t w = blockIdx.x * 4 + (threadIdx.x >> 6);
   const uint32_t lane = threadIdx.x & 63;
   if (w >= n) return;
   const Copy c = copies[w];
   if (!c.n) return;
-  uint64_t len = c.n;
-  const uint8_t* src = c.src;
-  uint8_t* dst = c.dst;
-  uint32_t head = (uint32_t)((16 - ((uintptr_t)dst & 15)) & 15);
-  if (head > len) head = (uint32_t)len;
-  if (lane < head) dst[lane] = src[lane];
-  src += head;
-  dst += head;
-  len -= head;
-  const uint64_t nv = len >> 4;
-  uint64_t v = lane;
-  // four 16-byte loads in flight per lane before their stores
-  for (; v + 3 * 64 < nv; v += 4 * 64) {
-    u32x4 x[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) __builtin_memcpy(&x[u], src + (v + u * 64) * 16, 16);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) __builtin_nontemporal_store(x[u], reinterpret_cast<u32x4*>(dst + (v + u * 64) * 16));
-  }
-  for (; v < nv; v += 64) {
-    u32x4 x;
-    __builtin_memcpy(&x, src + v * 16, 16);
-    __builtin_nontemporal_store(x, reinterpret_cast<u32x4*>(dst + v * 16));
-  }
-  const uint32_t t = (uint32_t)(len & 15);
-  if (lane < t) dst[nv * 16 + lane] = src[nv * 16 + lane];
+  zccopy::wave_copy(c.dst, c.src, c.n, lane);
 }
 
 __global__ void zc_lzo_or_kernel(uint8_t* out, const uint64_t* or_at, const uint32_t* or_val, uint32_t nb) {

@@ -14,11 +14,20 @@ lzo1x_decompress_safe, as the reference calls it, compression.cc:472-490;
 `bundle.frame_info` reads the frame): the instruction stream travels to the
 device in the same buffer, so there is one upload (`RestorePlan.host_image`;
 `RestorePlan.instruction_image` is the instruction stream's share of it alone).
+
+  IndexedRestorer::saveData  -> any byte range            backup_restorer.cc:182-316
+
+`IndexedRestorer` serves batches of (offset, size) reads from the payloads that
+are resident at the time (zc_range_read): the same plan, kept as a
+`RangeIndex` of (position, slot, offset) entries in HBM, one slot per
+referenced bundle and one for the instruction stream.
 """
+import ctypes
+
 import numpy as np
 
 from . import _lib
-from .bundle import BundleCompressor, parse_backup_data
+from .bundle import BundleCompressor, _u64, parse_backup_data
 
 
 def chunk_map(bundles):
@@ -130,6 +139,176 @@ class Restorer:
 
     def close(self):
         self._comp.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def _range_check(L, ctx, rc, what):
+    if rc != _lib.ZC_OK:
+        msg = L.zc_last_error(ctx) or b""
+        raise _lib.ZcError(f"{what} failed ({rc}): {msg.decode(errors='replace')}")
+
+
+class RangeIndex:
+    """A zc_range_index: entry e of the stream is sizes[e] bytes at off[e] of
+    slot[e]; a slot is one resident payload of slot_sizes[k] bytes.  `comp`, a
+    BundleCompressor, gives the context whose device holds the index and whose
+    stream runs the reads; without one the index is host only (`total`,
+    `needs` and every argument check work)."""
+
+    def __init__(self, slot_sizes, slot, off, sizes, comp=None):
+        self._L = _lib.load()
+        self._ctx = comp._ctx if comp is not None else None
+        slot_sizes, off, sizes = _u64(slot_sizes), _u64(off), _u64(sizes)
+        slot = np.ascontiguousarray(np.asarray(slot, dtype=np.uint32))
+        if not len(slot) == len(off) == len(sizes):
+            raise ValueError("RangeIndex: slot, off and sizes differ in length")
+        self._idx = ctypes.c_void_p()
+        rc = self._L.zc_range_index_create(self._ctx, slot_sizes.ctypes.data, len(slot_sizes), slot.ctypes.data,
+                                           off.ctypes.data, sizes.ctypes.data, len(sizes), ctypes.byref(self._idx))
+        _range_check(self._L, self._ctx, rc, "zc_range_index_create")
+        total = ctypes.c_uint64()
+        self._L.zc_range_index_total(self._idx, ctypes.byref(total))
+        self.total = total.value
+        self.n_slots = len(slot_sizes)
+
+    def set_slot(self, slot, d_ptr):
+        """Caller-owned device memory of the slot's size; None clears it."""
+        _range_check(self._L, None, self._L.zc_range_set_slot(self._idx, int(slot), d_ptr), "zc_range_set_slot")
+
+    def upload_slot(self, slot, payload):
+        """A copy of host bytes the index owns; their length must be the slot's size."""
+        payload = bytes(payload)
+        buf = np.frombuffer(payload or b"\0", dtype=np.uint8)
+        rc = self._L.zc_range_slot_upload(self._idx, int(slot), buf.ctypes.data, len(payload))
+        _range_check(self._L, None, rc, "zc_range_slot_upload")
+
+    def drop_slot(self, slot):
+        _range_check(self._L, None, self._L.zc_range_slot_drop(self._idx, int(slot)), "zc_range_slot_drop")
+
+    @staticmethod
+    def _reads(reads):
+        if not isinstance(reads, np.ndarray):
+            reads = list(reads)
+        r = np.asarray(reads, dtype=np.uint64).reshape(-1, 2)
+        return np.ascontiguousarray(r[:, 0]), np.ascontiguousarray(r[:, 1])
+
+    def needs(self, reads):
+        """The distinct slots the reads [(offset, size), ...] touch, ascending."""
+        offset, size = self._reads(reads)
+        out = np.zeros(max(self.n_slots, 1), dtype=np.uint32)
+        n = ctypes.c_size_t()
+        rc = self._L.zc_range_needs(self._idx, offset.ctypes.data, size.ctypes.data, len(offset), out.ctypes.data,
+                                    self.n_slots, ctypes.byref(n))
+        _range_check(self._L, None, rc, "zc_range_needs")
+        return [int(s) for s in out[:n.value]]
+
+    def read(self, reads, d_out, dst_off):
+        """One batch: read i's bytes to d_out + dst_off[i] (device memory)."""
+        offset, size = self._reads(reads)
+        dst_off = _u64(dst_off)
+        if len(dst_off) != len(offset):
+            raise ValueError("RangeIndex.read: reads and dst_off differ in length")
+        rc = self._L.zc_range_read(self._ctx, self._idx, offset.ctypes.data, size.ctypes.data, len(offset), d_out,
+                                   dst_off.ctypes.data)
+        _range_check(self._L, self._ctx, rc, "zc_range_read")
+
+    def read_host(self, reads):
+        """The reads' bytes, one bytes object each, through the pinned staging buffer."""
+        offset, size = self._reads(reads)
+        dst_off = (np.concatenate([[0], np.cumsum(size)[:-1]]).astype(np.uint64) if len(size)
+                   else np.zeros(0, dtype=np.uint64))
+        out = np.zeros(max(int(size.sum()), 1), dtype=np.uint8)
+        rc = self._L.zc_range_read_host(self._ctx, self._idx, offset.ctypes.data, size.ctypes.data, len(offset),
+                                        out.ctypes.data, dst_off.ctypes.data)
+        _range_check(self._L, self._ctx, rc, "zc_range_read_host")
+        return [out[int(o):int(o) + int(n)].tobytes() for o, n in zip(dst_off, size)]
+
+    def last_stats(self):
+        """(upload ms, kernel ms, pieces) of the context's last read."""
+        up, kern, pieces = ctypes.c_double(), ctypes.c_double(), ctypes.c_uint64()
+        rc = self._L.zc_range_last_stats(self._ctx, ctypes.byref(up), ctypes.byref(kern), ctypes.byref(pieces))
+        _range_check(self._L, self._ctx, rc, "zc_range_last_stats")
+        return up.value, kern.value, pieces.value
+
+    def close(self):
+        if self._idx:
+            self._L.zc_range_index_destroy(self._idx)
+            self._idx = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class IndexedRestorer:
+    """Any byte range of a backup from the bundle payloads resident at the
+    time: BackupRestorer::IndexedRestorer on the GPU.  Built on Restorer.plan's
+    parse and id map: slot k is the decoded payload of bundle `plan.used[k]`,
+    the last slot the instruction stream, uploaded here.  Reads are
+    (offset, size) pairs; `needs` tells which bundles a batch wants resident.
+    device=None makes a host-only object (`size`, `needs`), for planning."""
+
+    def __init__(self, backup_data, bundles, device=0, ctx=None):
+        plan = Restorer.plan(backup_data, bundles)
+        self.plan = plan
+        self._comp = BundleCompressor(device=device, ctx=ctx) if device is not None or ctx is not None else None
+        pay_off = np.asarray(plan.pay_off, dtype=np.uint64)
+        in_instr = plan.src_off >= np.uint64(plan.instr_off)
+        k = np.searchsorted(pay_off, plan.src_off, side="right").astype(np.int64) - 1
+        k[in_instr] = len(plan.used)
+        base = np.concatenate([pay_off, [plan.instr_off]]).astype(np.uint64)
+        self._slot_of = {b: i for i, b in enumerate(plan.used)}
+        self._index = None
+        try:
+            self._index = RangeIndex(list(plan.pay_size) + [len(plan.data)], k, plan.src_off - base[k], plan.sizes,
+                                     comp=self._comp)
+            self.size = self._index.total
+            if self._comp is not None:
+                self._index.upload_slot(len(plan.used), plan.data)
+        except Exception:
+            self.close()  # the context made above does not outlive a failed construction
+            raise
+
+    def _slot(self, bundle):
+        if bundle not in self._slot_of:
+            raise _lib.ZcError(f"bundle {bundle} is not one the stream references")
+        return self._slot_of[bundle]
+
+    def needs(self, reads):
+        """The bundles (indices into `bundles`) whose payloads the reads touch."""
+        return [self.plan.used[s] for s in self._index.needs(reads) if s < len(self.plan.used)]
+
+    def set_payload(self, bundle, d_ptr):
+        """The bundle's decoded payload in caller-owned device memory."""
+        self._index.set_slot(self._slot(bundle), d_ptr)
+
+    def upload_payload(self, bundle, payload):
+        self._index.upload_slot(self._slot(bundle), payload)
+
+    def drop_payload(self, bundle):
+        self._index.drop_slot(self._slot(bundle))
+
+    def read(self, reads, d_out, dst_off):
+        self._index.read(reads, d_out, dst_off)
+
+    def read_host(self, offset, size):
+        return self._index.read_host([(offset, size)])[0]
+
+    def last_stats(self):
+        return self._index.last_stats()
+
+    def close(self):
+        if self._index is not None:
+            self._index.close()
+        if self._comp is not None:
+            self._comp.close()
 
     def __enter__(self):
         return self
