@@ -245,6 +245,43 @@ enum {
   ZC_PATH_TABLES_CLEARED_BY_EPOCH = 8  /* an index launch cleared the tables itself (the non-fused form) */
 };
 int zc_last_stream_paths(const zc_ctx* ctx, uint32_t* bits);
+/* What the scan left behind for the context's last stream (tests only; a caller needs none of it):
+ * every word the scan kernel, the tail kernel and the exact rescan of overflowed wave-tiles wrote,
+ * copied out of the buffers the context keeps.  The call holds the context's lock, waits for its
+ * stream and copies; it launches nothing.  Valid after a finished zc_chunk_device / zc_chunk_host
+ * (or a zc_finish with the window set to 0); ZC_ERR_STATE with a message before any stream and
+ * after a stream through the feed window (the buffers then hold the window); kept across zc_reset.
+ * The caller sets the arrays and their capacities (elements), the call sets the counts:
+ *   n, blk[0, n_blk)          the stream's length; the 64-bit digest of every 1 KiB span, n_blk =
+ *                             ceil(n / 1024), the partial last span included (the Horner value of
+ *                             the bytes present)
+ *   wt_count / wt_side[0, n_wt)  per 256 KiB wave-tile t < ceil(n / 256 KiB): its anchors, and 1 when
+ *                             its directory entry points into the side pool (it was rescanned exactly)
+ *   anchor_pos / anchor_gear[0, n_anchors)  the anchors of all wave-tiles in wave-tile order, as the
+ *                             directory lists them: stream position and the 32-bit gear word
+ *   keys[0, n_keys)           the grid keys the scan wrote (key i: chunk [i W, (i + 1) W) of the full
+ *                             2 MiB tiles), while they are still the scan's: a stream of one epoch
+ *                             (zc_stats.epochs == 1) whose epoch took them as they were; else n_keys = 0
+ *   max_tiles_per_wave        the most wave-tiles one wave walked in a scan-kernel launch of the stream
+ * ZC_ERR_ARG with the counts set when an array is missing or too small (all capacities 0 asks for the
+ * counts); ZC_ERR_STATE when a wave-tile is still marked overflowed, a directory entry points outside
+ * its pool, or the pinned host copy of the keys differs from the device's (errors of the engine). */
+typedef struct zc_scan_outputs {
+  uint64_t n;
+  uint64_t* blk;
+  size_t blk_cap, n_blk;
+  uint32_t* wt_count;
+  uint8_t* wt_side;
+  size_t wt_cap, n_wt;
+  uint64_t* anchor_pos;
+  uint32_t* anchor_gear;
+  size_t anchor_cap, n_anchors;
+  uint64_t* keys;
+  size_t key_cap, n_keys;
+  uint32_t max_tiles_per_wave;
+  uint32_t reserved;
+} zc_scan_outputs;
+int zc_debug_scan_outputs(const zc_ctx* ctx, zc_scan_outputs* out);
 int zc_reset(zc_ctx* ctx); /* begin a new stream (the seeded index is kept) */
 /* drop the index entries this context's streams added (ZC_FLAG_SHA1: Writer::add ->
  * ChunkIndex::addChunk, chunk_storage.cc:31-46), keeping the seeded ones.  Only for streams

@@ -48,6 +48,7 @@ def test_abi_version_and_argument_errors(lib):
     assert lib.zc_destroy(None) == _lib.ZC_ERR_ARG
     assert lib.zc_record_count(None) == 0
     assert lib.zc_last_stream_paths(None, ctypes.byref(ctypes.c_uint32())) == _lib.ZC_ERR_ARG
+    assert lib.zc_debug_scan_outputs(None, ctypes.byref(_lib.ZcScanOutputs())) == _lib.ZC_ERR_ARG
     assert lib.zc_last_error(None) == b"null context"
 
 

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle
+from tests.scan_ref import model_anchors
 
 pytestmark = pytest.mark.gpu
 
@@ -21,26 +22,6 @@ def torch_cuda():
     from zbackup_amd import _build
     _build.build()
     return torch
-
-
-def _rate_inv(W):
-    r = 16
-    while r < 4096 and r * 2 <= W // 16:
-        r *= 2
-    return r
-
-
-def model_anchors(data, W):
-    """The anchor positions of `data` at chunk size W (a bool per position)."""
-    b = data.astype(np.uint32)
-    st = np.zeros(b.size, dtype=np.uint32)
-    for j in range(16):
-        st[2 * j:] += b[:b.size - 2 * j] << np.uint32(j)
-    s16 = (st & 0xFFFF).astype(np.uint16).view(np.int16)
-    lo = 0x8000 - 0x10000 // _rate_inv(W)
-    hit = s16 >= lo
-    hit[:63] = False
-    return hit
 
 
 def model_anchor_count(data, W):

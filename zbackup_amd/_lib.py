@@ -29,7 +29,7 @@ EXPORTS = ["zc_create", "zc_destroy", "zc_seed_index", "zc_get_input_buffer",
            "zc_chunk_meta_compute", "zc_chunk_meta_compute_host", "zc_meta_last_stats",
            "zc_range_index_create", "zc_range_index_total", "zc_range_index_destroy", "zc_range_set_slot",
            "zc_range_slot_upload", "zc_range_slot_drop", "zc_range_needs", "zc_range_read", "zc_range_read_host",
-           "zc_range_last_stats"]
+           "zc_range_last_stats", "zc_debug_scan_outputs"]
 ZC_META_BAD_SHA1, ZC_META_BAD_ROLLING, ZC_META_BAD_SIZE = 1, 2, 4
 ZC_GC_DEEP, ZC_GC_REPACK, ZC_GC_CONCAT = 1, 2, 4
 ZC_GC_ACT_KEEP, ZC_GC_ACT_REMOVE, ZC_GC_ACT_REPACK, ZC_GC_ACT_DROP_RECORD = 0, 1, 2, 3
@@ -101,6 +101,15 @@ class ZcGcOutput(ctypes.Structure):
                 ("new_bundle_cap", ctypes.c_uint64), ("n_new_bundles", ctypes.c_uint64)]
 
 
+class ZcScanOutputs(ctypes.Structure):
+    _fields_ = [("n", ctypes.c_uint64), ("blk", ctypes.c_void_p), ("blk_cap", ctypes.c_size_t),
+                ("n_blk", ctypes.c_size_t), ("wt_count", ctypes.c_void_p), ("wt_side", ctypes.c_void_p),
+                ("wt_cap", ctypes.c_size_t), ("n_wt", ctypes.c_size_t), ("anchor_pos", ctypes.c_void_p),
+                ("anchor_gear", ctypes.c_void_p), ("anchor_cap", ctypes.c_size_t), ("n_anchors", ctypes.c_size_t),
+                ("keys", ctypes.c_void_p), ("key_cap", ctypes.c_size_t), ("n_keys", ctypes.c_size_t),
+                ("max_tiles_per_wave", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
 class ZcStats(ctypes.Structure):
     _fields_ = [("scan_ms", ctypes.c_double), ("resolve_ms", ctypes.c_double),
                 ("total_ms", ctypes.c_double), ("bytes", ctypes.c_uint64),
@@ -153,6 +162,7 @@ def load(path=LIB_PATH):
         "zc_get_records": (i32, [vp, ctypes.POINTER(ZcRecord), sz, ctypes.POINTER(sz)]),
         "zc_get_stats": (i32, [vp, ctypes.POINTER(ZcStats)]),
         "zc_last_stream_paths": (i32, [vp, ctypes.POINTER(u32)]),
+        "zc_debug_scan_outputs": (i32, [vp, ctypes.POINTER(ZcScanOutputs)]),
         "zc_reset": (i32, [vp]),
         "zc_last_error": (ctypes.c_char_p, [vp]),
         "zc_fill_splitmix64": (i32, [vp, u64, u64, i32]),

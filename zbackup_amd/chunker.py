@@ -309,6 +309,33 @@ class BackupCreator:
                "zc_last_stream_paths")
         return bits.value
 
+    def scan_outputs(self):
+        """zc_debug_scan_outputs (tests): what the scan left behind for the last
+        stream, as a dict: n, blk (uint64 per 1 KiB span), wt_count / wt_side
+        (per 256 KiB wave-tile), anchor_pos (uint64) / anchor_gear (uint32) in
+        wave-tile order, keys (the scan-written grid keys, empty when they are
+        no longer the scan's), max_tiles_per_wave.  Raises ZcError before any
+        stream and after a stream through the feed window."""
+        o = _lib.ZcScanOutputs()
+        rc = self._L.zc_debug_scan_outputs(self._ctx, ctypes.byref(o))  # all capacities 0: the counts
+        if rc == _lib.ZC_ERR_ARG and self._ctx:
+            blk = np.zeros(o.n_blk, dtype=np.uint64)
+            wt_count, wt_side = np.zeros(o.n_wt, dtype=np.uint32), np.zeros(o.n_wt, dtype=np.uint8)
+            pos, gear = np.zeros(o.n_anchors, dtype=np.uint64), np.zeros(o.n_anchors, dtype=np.uint32)
+            keys = np.zeros(o.n_keys, dtype=np.uint64)
+            o.blk, o.blk_cap = blk.ctypes.data, blk.size
+            o.wt_count, o.wt_side, o.wt_cap = wt_count.ctypes.data, wt_side.ctypes.data, wt_count.size
+            o.anchor_pos, o.anchor_gear, o.anchor_cap = pos.ctypes.data, gear.ctypes.data, pos.size
+            o.keys, o.key_cap = keys.ctypes.data, keys.size
+            rc = self._L.zc_debug_scan_outputs(self._ctx, ctypes.byref(o))
+        else:  # an empty stream needs no room
+            blk = keys = pos = np.zeros(0, dtype=np.uint64)
+            wt_count = gear = np.zeros(0, dtype=np.uint32)
+            wt_side = np.zeros(0, dtype=np.uint8)
+        _check(self._L, self._ctx, rc, "zc_debug_scan_outputs")
+        return {"n": int(o.n), "blk": blk, "wt_count": wt_count, "wt_side": wt_side, "anchor_pos": pos,
+                "anchor_gear": gear, "keys": keys, "max_tiles_per_wave": int(o.max_tiles_per_wave)}
+
     def scan_ms(self):
         """zc_stats.scan_ms of the last stream, without building the stats dict
         (bench.py reads it inside its timed loop)."""

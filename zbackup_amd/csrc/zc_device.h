@@ -252,7 +252,10 @@ hipError_t launch_scan(const uint8_t* data, uint64_t n, int32_t anchor_lo, uint6
 hipError_t launch_scan_tiles(const uint8_t* data, uint64_t n, uint64_t tile0, uint64_t ntiles, int32_t anchor_lo,
                              uint64_t* blk, PoolOut po, unsigned long long* counters, hipStream_t s,
                              GridKeysOut gko = GridKeysOut{nullptr, nullptr, 0, 0}, hipEvent_t start = nullptr,
-                             hipEvent_t stop = nullptr);
+                             hipEvent_t stop = nullptr, uint32_t max_wgs = 0, uint32_t* tiles_per_wave = nullptr);
+// (max_wgs: tests only, ZC_TEST_SCAN_WGS -- at most that many workgroups, so a
+// wave walks several wave-tiles on a stream of a few MiB; 0: no cap.
+// tiles_per_wave: receives the most wave-tiles one wave of this launch walks.)
 // the W for which the scan can write the grid keys (GridKeysOut), else 0
 inline uint32_t scan_key_lshift_or_none(uint32_t W, bool& ok) {
   ok = W >= (uint32_t)ZC_LSPAN && W % ZC_LSPAN == 0 && ((64u * ZC_LSPAN) % W) == 0;

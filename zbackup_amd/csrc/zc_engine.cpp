@@ -515,6 +515,16 @@ struct zc_ctx {
   // where a stream starts; and of the last stream finished
   uint32_t paths = 0, paths_last = 0;
   bool paths_valid = false;
+  // what zc_debug_scan_outputs reports of the last stream finished (tests):
+  // whether it was a whole-stream one (its position-indexed buffers start at
+  // byte 0), the grid keys of c_key that are still the scan's, and the most
+  // wave-tiles one wave walked in a scan launch
+  bool scan_out_valid = false;
+  uint64_t scan_out_n = 0;  // its length (zc_reset clears n_last)
+  uint64_t scan_out_keys = 0;
+  uint32_t scan_out_tpw = 0;
+  // ZC_TEST_SCAN_WGS (tests): at most this many workgroups per scan launch; 0: no cap
+  uint32_t test_scan_wgs = 0;
   HostBuf<unsigned long long> h_co_hc;
   HostBuf<Cand> h_hist_cand;  // the historic candidates, key-checked and in position order
   HostBuf<uint32_t> h_cls;  // the epoch's content classes (likewise)
@@ -894,8 +904,10 @@ class Resolver {
       const GridKeysOut gko = scan_keys_ ? GridKeysOut{c_.c_key.p, c_.h_key.p, pow257(W_), key_lshift_}
                                          : GridKeysOut{nullptr, nullptr, 0, 0};
       hipEvent_t stop = last ? scan_end_event() : nullptr;
+      uint32_t tpw = 0;
       HCK(launch_scan_tiles(d_, n_, tiles_done_, t1 - tiles_done_, anchor_lo_, blk_v(), pool_out(), c_.scnt.p,
-                            c_.stream, gko, start, stop));
+                            c_.stream, gko, start, stop, c_.test_scan_wgs, &tpw));
+      scan_tpw_ = std::max(scan_tpw_, tpw);
       scan_end_recorded_ = stop != nullptr;
       tiles_done_ = t1;
     }
@@ -955,6 +967,11 @@ class Resolver {
     }
     finalize_records(true);
     clear_tables();  // (normally done after the last epoch's probe already)
+    // for zc_debug_scan_outputs: c_key[0, tiles W-chunks) is the scan's while one
+    // epoch ran and took them as they were (a later epoch uploads its confirmed
+    // refs' keys over them; an epoch with key_from short of them recomputes them)
+    c_.scan_out_keys = scan_keys_ && !scan_keys_lost_ && c_.stats.epochs <= 1 ? tiles_done_ * ZC_STILE / W_ : 0;
+    c_.scan_out_tpw = scan_tpw_;
     const double ms = ms_since(t0);
     c_.stats.total_ms += ms;
     // the resolver's work overlaps the scan's tail (nothing waits for the scan
@@ -1174,6 +1191,8 @@ class Resolver {
   const uint32_t wcap_ = wave_tile_cap(W_);
   Clock::time_point t_begin_;
   uint64_t tiles_done_ = 0;  // full scan tiles launched
+  uint32_t scan_tpw_ = 0;    // most wave-tiles one wave walked in a scan launch
+  bool scan_keys_lost_ = false;  // an epoch recomputed grid keys the scan had written
   bool scan_open_ = false;   // scan launches queued since the last scan_finish
   bool scan_end_recorded_ = false;  // the last scan launch records the scan-end event itself
   uint64_t chk_wt_ = 0;      // wave-tiles below are checked for overflow
@@ -1484,6 +1503,8 @@ class Resolver {
           scan_keys_ && r_e_ == 0 && nconf_ == 0 && c_.c_key.cap >= nref_ && c_.h_key.cap >= nsref
               ? (uint32_t)std::min<uint64_t>(nsref, tiles_done_ * ZC_STILE / W_)
               : 0u;
+      if (scan_keys_ && nref_ && key_from != std::min<uint64_t>(nsref, tiles_done_ * ZC_STILE / W_))
+        scan_keys_lost_ = true;
       if (nref_) {
         c_.c_start.ensure(nref_);
         c_.c_key.ensure(nref_);
@@ -3170,6 +3191,7 @@ void window_open(zc_ctx& c) {
   c.wbase = c.wend = 0;
   c.windowed_last = true;
   c.paths = 0;
+  c.scan_out_valid = false;
   c.res = new Resolver(c, c.dwin.p, 0, true);
   c.res->begin();
 }
@@ -3243,6 +3265,8 @@ void stream_done(zc_ctx& c) {
   c.finished = true;
   c.paths_last = c.paths;
   c.paths_valid = true;
+  c.scan_out_valid = !c.windowed_last;
+  c.scan_out_n = c.n_last;
 }
 
 size_t ctx_hbm_bytes(const zc_ctx& c) {
@@ -3281,6 +3305,14 @@ int zc_create(zc_ctx** out, uint32_t chunk_max_size, int device, uint32_t flags)
   c->W = chunk_max_size;
   c->flags = flags;
   c->win_cap = window_for(kDefaultWindow, chunk_max_size);
+  // (ZC_TEST_SCAN_WGS: tests cap the scan's grid so that a wave walks several
+  // wave-tiles on a stream of a few MiB; read here once, never per stream.  A
+  // value that is no positive number is ignored; one above the grid caps nothing.)
+  if (const char* tw = getenv("ZC_TEST_SCAN_WGS")) {
+    char* end = nullptr;
+    const long v = strtol(tw, &end, 10);
+    if (end != tw && *end == 0 && v >= 1 && v <= 0x7FFFFFFFL) c->test_scan_wgs = (uint32_t)v;
+  }
   int rc = guarded(c, [&] {
     DeviceGuard g(device);
     HCK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
@@ -3575,6 +3607,7 @@ int zc_finish(zc_ctx* c) {
     DeviceGuard g(c->device);
     c->windowed_last = false;
     c->paths = 0;
+    c->scan_out_valid = false;  // (the buffers are being rewritten; stream_done sets it)
     Resolver res(*c, c->d_stream.p, c->n_stream, false);
     res.run();
     c->d_last = c->d_stream.p;
@@ -3601,6 +3634,7 @@ int zc_chunk_device(zc_ctx* c, const void* d_data, uint64_t n) {
     }
     c->windowed_last = false;
     c->paths = 0;
+    c->scan_out_valid = false;  // (the buffers are being rewritten; stream_done sets it)
     const uint32_t nh = c->nhist;
     const size_t ns = c->statics.size();
     bool redo = false;
@@ -3639,6 +3673,7 @@ int zc_chunk_host(zc_ctx* c, const void* host, uint64_t n) {
     c->n_stream = n;
     c->windowed_last = false;
     c->paths = 0;
+    c->scan_out_valid = false;  // (the buffers are being rewritten; stream_done sets it)
     uint8_t* d = c->d_stream.p;
     const uint8_t* h = (const uint8_t*)host;
     // segments land on the copy stream; the scan of each follows on the
@@ -3717,6 +3752,84 @@ int zc_last_stream_paths(const zc_ctx* cc, uint32_t* bits) {
   *bits = c->paths_last;
   c->err.clear();
   return ZC_OK;
+}
+
+// What the scan (zc_scan_kernel, the tail kernel, the exact rescan) left in the
+// context's buffers for the last stream: copies only, no kernel.
+int zc_debug_scan_outputs(const zc_ctx* cc, zc_scan_outputs* o) {
+  zc_ctx* c = const_cast<zc_ctx*>(cc);  // the message is the context's
+  ZC_LOCK(c);
+  if (!c || !o) return ZC_ERR_ARG;
+  if (!c->scan_out_valid) {
+    c->err = c->windowed_last ? "zc_debug_scan_outputs: the last stream came through the feed window (its buffers "
+                                "hold the window, not the stream)"
+                              : "zc_debug_scan_outputs: this context has finished no stream since its last one began";
+    return ZC_ERR_STATE;
+  }
+  return guarded(c, [&] {
+    DeviceGuard g(c->device);
+    HCK(hipStreamSynchronize(c->stream));
+    const uint64_t n = c->scan_out_n;
+    const uint64_t nblk = (n + ZC_SPAN - 1) / ZC_SPAN, nwt = (n + (1ull << ZC_WT_SHIFT) - 1) >> ZC_WT_SHIFT;
+    const uint64_t wcap = wave_tile_cap(c->W);
+    if (nblk > c->blk.cap || nwt > c->dbase.cap || nwt > c->dcnt.cap || c->scan_out_keys > c->c_key.cap ||
+        c->scan_out_keys > c->h_key.cap)
+      throw ZcError{ZC_ERR_STATE, "zc_debug_scan_outputs: the context's buffers are smaller than the stream"};
+    std::vector<uint32_t> base(nwt), cnt(nwt);
+    if (nwt) {
+      HCK(hipMemcpy(base.data(), c->dbase.p, nwt * sizeof(uint32_t), hipMemcpyDeviceToHost));
+      HCK(hipMemcpy(cnt.data(), c->dcnt.p, nwt * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+    uint64_t total = 0;
+    for (uint64_t t = 0; t < nwt; ++t) {
+      if (cnt[t] == 0xFFFFFFFFu)
+        throw ZcError{ZC_ERR_STATE, "zc_debug_scan_outputs: wave-tile " + std::to_string(t) +
+                                        " is still marked overflowed at the stream's end"};
+      const bool side = (base[t] & ZC_SIDE_POOL) != 0;
+      const uint64_t b = base[t] & ~ZC_SIDE_POOL;
+      // a main-pool entry must lie inside the wave-tile's own share
+      if (side ? b + cnt[t] > c->srel.cap || b + cnt[t] > c->sg.cap
+               : b != t * wcap || cnt[t] > wcap || b + cnt[t] > c->prel.cap || b + cnt[t] > c->pg.cap)
+        throw ZcError{ZC_ERR_STATE, "zc_debug_scan_outputs: the directory entry of wave-tile " + std::to_string(t) +
+                                        " points outside its pool"};
+      total += cnt[t];
+    }
+    o->n = n;
+    o->n_blk = nblk;
+    o->n_wt = nwt;
+    o->n_anchors = total;
+    o->n_keys = c->scan_out_keys;
+    o->max_tiles_per_wave = c->scan_out_tpw;
+    o->reserved = 0;
+    if ((nblk && !o->blk) || (nwt && (!o->wt_count || !o->wt_side)) || (total && (!o->anchor_pos || !o->anchor_gear)) ||
+        (o->n_keys && !o->keys) || o->blk_cap < nblk || o->wt_cap < nwt || o->anchor_cap < total ||
+        o->key_cap < o->n_keys)
+      throw ZcError{ZC_ERR_ARG, "zc_debug_scan_outputs: an output array is missing or too small (the counts "
+                                "needed are set)"};
+    if (nblk) HCK(hipMemcpy(o->blk, c->blk.p, nblk * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    std::vector<uint32_t> rel;
+    uint64_t at = 0;
+    for (uint64_t t = 0; t < nwt; ++t) {
+      const bool side = (base[t] & ZC_SIDE_POOL) != 0;
+      const uint64_t b = base[t] & ~ZC_SIDE_POOL;
+      o->wt_count[t] = cnt[t];
+      o->wt_side[t] = side ? 1 : 0;
+      if (!cnt[t]) continue;
+      rel.resize(cnt[t]);
+      HCK(hipMemcpy(rel.data(), (side ? c->srel.p : c->prel.p) + b, cnt[t] * sizeof(uint32_t), hipMemcpyDeviceToHost));
+      HCK(hipMemcpy(o->anchor_gear + at, (side ? c->sg.p : c->pg.p) + b, cnt[t] * sizeof(uint32_t),
+                    hipMemcpyDeviceToHost));
+      for (uint32_t k = 0; k < cnt[t]; ++k) o->anchor_pos[at + k] = (t << ZC_WT_SHIFT) + rel[k];
+      at += cnt[t];
+    }
+    if (o->n_keys) {
+      HCK(hipMemcpy(o->keys, c->c_key.p, o->n_keys * sizeof(uint64_t), hipMemcpyDeviceToHost));
+      // the scan stores every key twice: the host's pinned copy must agree
+      if (memcmp(o->keys, c->h_key.p, o->n_keys * sizeof(uint64_t)) != 0)
+        throw ZcError{ZC_ERR_STATE, "zc_debug_scan_outputs: the pinned host copy of the scan's grid keys differs "
+                                    "from the device's"};
+    }
+  });
 }
 
 int zc_reset(zc_ctx* c) {

@@ -3040,13 +3040,19 @@ static int cu_count() {
 
 hipError_t launch_scan_tiles(const uint8_t* data, uint64_t n, uint64_t tile0, uint64_t ntiles, int32_t anchor_lo,
                              uint64_t* blk, PoolOut po, unsigned long long* counters, hipStream_t s,
-                             GridKeysOut gko, hipEvent_t start, hipEvent_t stop) {
+                             GridKeysOut gko, hipEvent_t start, hipEvent_t stop, uint32_t max_wgs,
+                             uint32_t* tiles_per_wave) {
+  if (tiles_per_wave) *tiles_per_wave = 0;
   if (!ntiles) return hipSuccess;
   if (gko.key && (!gko.hkey || ((uint64_t)ZC_LSPAN << gko.lshift) > (1ull << ZC_WT_SHIFT))) return hipErrorInvalidValue;
   // the tiles' wave-tiles, a wave each at a time, kScanWgPerCu workgroups per CU
   const uint64_t wt0 = tile0 * (ZC_SCAN_TPB / 64), nwt = ntiles * (ZC_SCAN_TPB / 64);
-  const unsigned grid = (unsigned)std::min<uint64_t>((nwt + kScanWaves - 1) / kScanWaves,
-                                                     (uint64_t)cu_count() * kScanWgPerCu);
+  unsigned grid = (unsigned)std::min<uint64_t>((nwt + kScanWaves - 1) / kScanWaves,
+                                               (uint64_t)cu_count() * kScanWgPerCu);
+  // (a cap above the grid changes nothing, so values past 2 x CUs are ignored)
+  if (max_wgs && max_wgs < grid) grid = max_wgs;
+  // wave 0 walks wave-tiles 0, G, 2 G, ... of the launch: the most of any wave
+  if (tiles_per_wave) *tiles_per_wave = (uint32_t)((nwt - 1) / ((uint64_t)grid * kScanWaves) + 1);
   if (start || stop)
     hipExtLaunchKernelGGL(zc_scan_kernel, dim3(grid), dim3(64 * kScanWaves), 0, s, start, stop, 0, data, n, wt0, nwt,
                           anchor_lo, blk, po, counters, gko);
