@@ -53,6 +53,10 @@
  *                          read back out of decoded bundles (Bundle::Reader::get, bundle.cc:235-251)
  *   zc_range_read          BackupRestorer::IndexedRestorer::saveData, a batch of ranges per call
  *                          (zc_range_index_create: its constructor)     backup_restorer.cc:182-316
+ *   zc_index_load          ChunkIndex::loadIndex's read of every index file through
+ *                          IndexFile::Reader        chunk_index.cc:26-79, index_file.cc:44-76
+ *   zc_bundle_info_parse   Message::parse of a bundle file's BundleInfo      bundle.cc:157-218
+ *   zc_index_serialize     IndexFile::Writer's messages                     index_file.cc:18-42
  *   zc_last_error          the DEF_EX exceptions / CHECK aborts of the reference
  *                          (backup_creator.cc:112,165-166, chunk_index.hh:88-89)
  */
@@ -480,7 +484,7 @@ typedef struct zc_bundle_layout {
   int32_t status;     /* ZC_BUNDLE_*; the fields below are set as far as the file could be read */
   uint32_t reserved;
   uint64_t header_off, header_len;  /* BundleFileHeader's bytes, offsets into this bundle's plaintext */
-  uint64_t info_off, info_len;      /* BundleInfo's bytes (decoding the protobufs stays with the caller) */
+  uint64_t info_off, info_len;      /* BundleInfo's bytes (zc_bundle_info_parse reads its records) */
   uint64_t body_off, body_len;      /* the compressed body */
 } zc_bundle_layout;
 /* Bundle::Reader's file (bundle.cc:157-218) for n files d_files[file_off[i] ..+ file_size[i]):
@@ -669,6 +673,93 @@ int zc_range_read_host(zc_ctx* ctx, zc_range_index* idx, const uint64_t* offset,
 /* The context's last such call: device time of the piece list's upload and of the kernel, and
  * the number of pieces. */
 int zc_range_last_stats(const zc_ctx* ctx, double* upload_ms, double* kernel_ms, uint64_t* pieces);
+
+/* ---- Index files: a repository's chunk records from the files on disk ----
+ * ChunkIndex::loadIndex (chunk_index.cc:26-79) reads every index file through IndexFile::Reader
+ * (index_file.cc:44-76, message.cc:24-42, encrypted_file.cc:130-209).  A file's plaintext is
+ * [R: 16 random bytes, with a key only], varint32 len + FileHeader{version = 1}, pairs of
+ * varint32 len + IndexBundleHeader{id: 24 bytes} and varint32 len + BundleInfo, a varint32 0 (the
+ * header without an id), the little-endian Adler-32 of every byte before it [, PKCS#7 padding of
+ * 1..16 bytes with a key]; with a key the whole file is one CBC chain from the zero IV.  BundleInfo
+ * is repeated 0A <len> ChunkRecord, ChunkRecord is 0A 18 <24-byte id> and 10 <varint32 size> in
+ * either order (zbackup.proto:107-145).  Bytes after the Adler-32 of an unkeyed file are ignored.
+ * zc_index_load reads n files in one call -- CBC decrypt, frame walk, Adler-32 and record parse all
+ * on the device (zc_index_core.h is the reader) -- into flat arrays in zc_gc_input's layout.
+ *
+ * The reader is strict, as zc_parse_instructions is, and narrower than libprotobuf: a tag is the
+ * single byte the writer emits, a field appears at most once, no other field is accepted; a
+ * varint32 has at most 5 bytes and fits 32 bits.
+ *
+ * A bad file does not fail the call: it gets a status, the first failure met reading it front to
+ * back (the padding first: it fixes where the file ends; the Adler-32 last, where the reference
+ * checks it).  A file whose status is not ZC_INDEX_OK contributes no bundles and no records:
+ * index_first[i + 1] == index_first[i].  This departs from loadIndex, which has already handed on
+ * the records in front of the failure when the exception reaches it: a backup tool should not act
+ * on half a file.
+ * Callers detect these entry points by their symbols (the ABI version stays 5). */
+enum {
+  ZC_INDEX_OK = 0,
+  ZC_INDEX_BAD_SIZE = 1,      /* 0 bytes; with a key, not a multiple of 16 */
+  ZC_INDEX_BAD_PADDING = 2,   /* last byte not 1..16, or the pad bytes differ */
+  ZC_INDEX_TRUNCATED = 3,     /* a message's length varint or the message it announces runs past the
+                                 end of the file, or no room for R or the Adler-32 */
+  ZC_INDEX_BAD_VERSION = 4,   /* FileHeader.version is not 1 */
+  ZC_INDEX_BAD_MESSAGE = 5,   /* the strict rules are broken inside a message: a varint of more than 5
+                                 bytes or 32 bits, a field running past its message, another tag, a
+                                 repeated field, a missing required field */
+  ZC_INDEX_BAD_BUNDLE_ID = 6, /* a bundle id that is not 24 bytes */
+  ZC_INDEX_BAD_CHUNK_ID = 7,  /* a chunk id that is not 24 bytes */
+  ZC_INDEX_BAD_ADLER = 8      /* the stored Adler-32 does not match */
+};
+typedef struct zc_index_set zc_index_set;
+/* File i is d_files[file_off[i] ..+ file_size[i]) in device memory; key NULL: no encryption.
+ * *set receives the loaded arrays (destroy it with zc_index_set_destroy).  ZC_ERR_ARG, with a
+ * message and before any device work: NULL pointers, and with a key misaligned offsets / bases
+ * (zc_bundle_unseal's rules).  Runs on the context's stream after the work queued on the default
+ * stream so far, as the other bundle calls do.  ZC_ERR_STATE: a kernel met one of its own bounds
+ * (an internal error).  ZC_TEST_INDEX_TILE=<bytes> and ZC_TEST_INDEX_WAVE_MIN=<bytes> in the
+ * environment shrink the LDS tile and the length from which a BundleInfo gets a whole wave: tests
+ * only. */
+int zc_index_load(zc_ctx* ctx, const uint8_t* key, const void* d_files, const uint64_t* file_off,
+                  const uint64_t* file_size, size_t n, zc_index_set** set);
+/* the same with the files in host memory (one upload; the base needs no alignment) */
+int zc_index_load_host(zc_ctx* ctx, const uint8_t* key, const void* files, const uint64_t* file_off,
+                       const uint64_t* file_size, size_t n, zc_index_set** set);
+int zc_index_set_counts(const zc_index_set* set, uint64_t* n_files, uint64_t* n_bundles, uint64_t* n_records);
+/* Copies out host arrays in zc_gc_input's layout (a NULL pointer skips that array): ids
+ * (n_records x 24), sizes (n_records), bundle_first (n_bundles + 1), bundle_ids (n_bundles x 24),
+ * index_first (n_files + 1), and status (n_files, ZC_INDEX_*). */
+int zc_index_set_fetch(const zc_index_set* set, uint8_t* ids, uint32_t* sizes, uint64_t* bundle_first,
+                       uint8_t* bundle_ids, uint64_t* index_first, int32_t* status);
+/* the device pointers of ids and sizes (NULL with no records), for consumers that stay in HBM;
+ * they live as long as the set */
+int zc_index_set_device(const zc_index_set* set, const void** d_ids, const void** d_sizes);
+int zc_index_set_destroy(zc_index_set* set);
+/* The record kernels alone over the BundleInfo bodies of n unsealed bundle files: bundle i's is
+ * d_plain[info_off[i] ..+ info_len[i]) (zc_bundle_layout's info_off is relative to its bundle's
+ * plaintext: add plain_off[i]).  status[i] receives ZC_INDEX_OK, _BAD_MESSAGE or _BAD_CHUNK_ID; a bad
+ * BundleInfo contributes no records.  ids (cap x 24), sizes (cap) and bundle_first (n + 1) are
+ * host arrays; *n_records = the records found, also when cap is too small (ZC_ERR_ARG). */
+int zc_bundle_info_parse(zc_ctx* ctx, const void* d_plain, const uint64_t* info_off, const uint64_t* info_len,
+                         size_t n, uint8_t* ids, uint32_t* sizes, uint64_t cap, uint64_t* bundle_first,
+                         uint8_t* status, uint64_t* n_records);
+int zc_bundle_info_parse_host(zc_ctx* ctx, const void* plain, const uint64_t* info_off, const uint64_t* info_len,
+                              size_t n, uint8_t* ids, uint32_t* sizes, uint64_t cap, uint64_t* bundle_first,
+                              uint8_t* status, uint64_t* n_records);
+/* Host only, the inverse: the plaintext between R and the Adler-32 (FileHeader, the bundles, the
+ * terminator) for n_bundles bundles in zc_gc_input's layout, as IndexFile::Writer emits it.
+ * *n_out = the bytes needed, also when cap is too small (ZC_ERR_ARG; message in
+ * zc_last_error(NULL), per thread). */
+int zc_index_serialize(const uint8_t* ids, const uint32_t* sizes, const uint64_t* bundle_first,
+                       const uint8_t* bundle_ids, uint64_t n_bundles, void* out, uint64_t cap, uint64_t* n_out);
+/* bytes of the whole file around `body` serialized bytes: keyed (16 + body + 4) / 16 * 16 + 16,
+ * else body + 4 */
+uint64_t zc_index_file_size(uint64_t body, int keyed);
+/* The context's last zc_index_load or zc_bundle_info_parse: time on the stream of the decrypt,
+ * the Adler-32 (its read-back included), the frame kernel and the record passes (gather, count,
+ * scan, write), and the whole call's wall clock. */
+int zc_index_last_stats(const zc_ctx* ctx, double* decrypt_ms, double* adler_ms, double* frame_ms,
+                        double* records_ms, double* total_ms);
 
 int zc_abi_version(void);
 /* digest of the sources this library was built from (zbackup_amd/_build.py

@@ -29,7 +29,15 @@ EXPORTS = ["zc_create", "zc_destroy", "zc_seed_index", "zc_get_input_buffer",
            "zc_chunk_meta_compute", "zc_chunk_meta_compute_host", "zc_meta_last_stats",
            "zc_range_index_create", "zc_range_index_total", "zc_range_index_destroy", "zc_range_set_slot",
            "zc_range_slot_upload", "zc_range_slot_drop", "zc_range_needs", "zc_range_read", "zc_range_read_host",
-           "zc_range_last_stats", "zc_debug_scan_outputs"]
+           "zc_range_last_stats", "zc_debug_scan_outputs",
+           "zc_index_load", "zc_index_load_host", "zc_index_set_counts", "zc_index_set_fetch", "zc_index_set_device",
+           "zc_index_set_destroy", "zc_bundle_info_parse", "zc_bundle_info_parse_host", "zc_index_serialize",
+           "zc_index_file_size", "zc_index_last_stats"]
+(ZC_INDEX_OK, ZC_INDEX_BAD_SIZE, ZC_INDEX_BAD_PADDING, ZC_INDEX_TRUNCATED, ZC_INDEX_BAD_VERSION, ZC_INDEX_BAD_MESSAGE,
+ ZC_INDEX_BAD_BUNDLE_ID, ZC_INDEX_BAD_CHUNK_ID, ZC_INDEX_BAD_ADLER) = range(9)
+INDEX_STATUS_NAMES = {0: "ok", 1: "bad file size", 2: "bad padding", 3: "truncated", 4: "unsupported version",
+                      5: "malformed message", 6: "bundle id is not 24 bytes", 7: "chunk id is not 24 bytes",
+                      8: "Adler-32 mismatch"}
 ZC_META_BAD_SHA1, ZC_META_BAD_ROLLING, ZC_META_BAD_SIZE = 1, 2, 4
 ZC_GC_DEEP, ZC_GC_REPACK, ZC_GC_CONCAT = 1, 2, 4
 ZC_GC_ACT_KEEP, ZC_GC_ACT_REMOVE, ZC_GC_ACT_REPACK, ZC_GC_ACT_DROP_RECORD = 0, 1, 2, 3
@@ -232,6 +240,21 @@ def load(path=LIB_PATH):
         "zc_range_read_host": (i32, [vp, vp, vp, vp, sz, vp, vp]),
         "zc_range_last_stats": (i32, [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                       ctypes.POINTER(u64)]),
+        # index files: (ctx, key, files, file_off, file_size, n, &set)
+        "zc_index_load": (i32, [vp, vp, vp, vp, vp, sz, ctypes.POINTER(vp)]),
+        "zc_index_load_host": (i32, [vp, vp, vp, vp, vp, sz, ctypes.POINTER(vp)]),
+        "zc_index_set_counts": (i32, [vp, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64)]),
+        # (set, ids, sizes, bundle_first, bundle_ids, index_first, status)
+        "zc_index_set_fetch": (i32, [vp, vp, vp, vp, vp, vp, vp]),
+        "zc_index_set_device": (i32, [vp, ctypes.POINTER(vp), ctypes.POINTER(vp)]),
+        "zc_index_set_destroy": (i32, [vp]),
+        # (ctx, plain, info_off, info_len, n, ids, sizes, cap, bundle_first, status, &n_records)
+        "zc_bundle_info_parse": (i32, [vp, vp, vp, vp, sz, vp, vp, u64, vp, vp, ctypes.POINTER(u64)]),
+        "zc_bundle_info_parse_host": (i32, [vp, vp, vp, vp, sz, vp, vp, u64, vp, vp, ctypes.POINTER(u64)]),
+        # (ids, sizes, bundle_first, bundle_ids, n_bundles, out, cap, &n_out)
+        "zc_index_serialize": (i32, [vp, vp, vp, vp, u64, vp, u64, ctypes.POINTER(u64)]),
+        "zc_index_file_size": (u64, [u64, i32]),
+        "zc_index_last_stats": (i32, [vp] + [ctypes.POINTER(ctypes.c_double)] * 5),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

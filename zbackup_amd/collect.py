@@ -98,6 +98,13 @@ class Collector:
         return self.plan_arrays(_ids(ids), sizes, bundle_first, _ids(bundle_ids), index_first, deep=deep,
                                 repack=repack, concat=concat, max_payload=max_payload)
 
+    def plan_index(self, index_set, **kw):
+        """The same from an IndexSet (IndexLoader.load): the records of the
+        index files as read from disk.  Files whose status is not 0 contribute
+        nothing, so the caller decides first whether to go on without them."""
+        return self.plan_arrays(index_set.ids, index_set.sizes, index_set.bundle_first, index_set.bundle_ids,
+                                index_set.index_first, **kw)
+
     def plan_arrays(self, ids, sizes, bundle_first, bundle_ids, index_first, deep=False, repack=False, concat=False,
                     max_payload=MAX_PAYLOAD_SIZE, copy_cap=None):
         """The same over flat arrays (zc_gc_input's fields)."""

@@ -598,4 +598,35 @@ int range_validate_read(zc_range_index* ix, const uint64_t* offset, const uint64
 int range_read(RangeScratch* s, zc_range_index* ix, const uint64_t* offset, const uint64_t* size, size_t n_reads,
                void* dst, const uint64_t* dst_off, bool host, hipEvent_t ev_in, hipStream_t st, std::string& err);
 
+// zc_index.hip: index files and BundleInfo bodies (zc_index_core.h).
+// index_validate / info_validate check what the host can see (no device, no
+// context); each call returns a zc_status with its message in `err`.
+struct IndexScratch;
+struct IndexTimes {
+  double decrypt_ms, adler_ms, frame_ms, records_ms, total_ms;
+};
+IndexScratch* index_scratch_new();
+void index_scratch_free(IndexScratch* s);
+const IndexTimes* index_times(const IndexScratch* s);
+int index_validate(const uint8_t* key, bool host, const void* files, const uint64_t* file_off,
+                   const uint64_t* file_size, size_t n, zc_index_set** set, std::string& err);
+// host: the files are in host memory (copied to HBM first); else ev_in orders
+// the context stream after the legacy default stream
+int index_load(IndexScratch* s, AesScratch* aes, LzoScratch* lz, bool host, const uint8_t* key, const void* files,
+               const uint64_t* file_off, const uint64_t* file_size, size_t n, zc_index_set** out, hipEvent_t ev_in,
+               hipStream_t st, std::string& err);
+int info_validate(bool host, const void* plain, const uint64_t* info_off, const uint64_t* info_len, size_t n,
+                  const uint64_t* bundle_first, const uint8_t* status, const uint64_t* n_records, std::string& err);
+int info_parse(IndexScratch* s, bool host, const void* plain, const uint64_t* info_off, const uint64_t* info_len,
+               size_t n, uint8_t* ids, uint32_t* sizes, uint64_t cap, uint64_t* bundle_first, uint8_t* status,
+               uint64_t* n_records, hipEvent_t ev_in, hipStream_t st, std::string& err);
+void index_set_counts(const zc_index_set* set, uint64_t* n_files, uint64_t* n_bundles, uint64_t* n_records);
+int index_set_fetch(const zc_index_set* set, uint8_t* ids, uint32_t* sizes, uint64_t* bundle_first,
+                    uint8_t* bundle_ids, uint64_t* index_first, int32_t* status, std::string& err);
+void index_set_device(const zc_index_set* set, const void** d_ids, const void** d_sizes);
+void index_set_destroy(zc_index_set* set);
+int index_serialize(const uint8_t* ids, const uint32_t* sizes, const uint64_t* bundle_first,
+                    const uint8_t* bundle_ids, uint64_t n_bundles, uint8_t* out, uint64_t cap, uint64_t* n_out,
+                    std::string& err);
+
 }  // namespace zc

@@ -542,6 +542,7 @@ struct zc_ctx {
   GcScratch* gc = nullptr;    // garbage collection's tables (zc_gc.hip), made on first use
   MetaScratch* meta = nullptr;  // adoption's buffers (zc_meta.hip), made on first use
   RangeScratch* range = nullptr;  // random-access restore's buffers (zc_range.hip), made on first use
+  IndexScratch* index = nullptr;  // index files' buffers (zc_index.hip), made on first use
 
   // scratch
   DevBuf<uint64_t> hm_key, hm_fp, hm_rkey;  // metadata of chunks joining the historic index
@@ -3365,6 +3366,7 @@ int zc_destroy(zc_ctx* c) {
     gc_scratch_free(c->gc);
     meta_scratch_free(c->meta);
     range_scratch_free(c->range);
+    index_scratch_free(c->index);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     if (prev >= 0) (void)hipSetDevice(prev);
@@ -4569,5 +4571,135 @@ int zc_range_last_stats(const zc_ctx* c, double* upload_ms, double* kernel_ms, u
   if (upload_ms) *upload_ms = t.upload_ms;
   if (kernel_ms) *kernel_ms = t.kernel_ms;
   if (pieces) *pieces = t.pieces;
+  return ZC_OK;
+}
+
+// ---- index files: decrypt, check, parse (zc_index.hip) ----
+
+// the common frame of the device calls below: `checked` is the host-side
+// validation's result, looked at before the context; f(err) does the work
+template <class F>
+static int index_entry(zc_ctx* c, const char* what, int checked, std::string& err, F&& f) {
+  if (checked != ZC_OK) return ctx_arg_error(c, (std::string(what) + ": " + err).c_str());
+  if (!c) return ctx_arg_error(c, (std::string(what) + ": null context").c_str());
+  int rc;
+  try {
+    DeviceGuard g(c->device);
+    if (!c->aes) c->aes = aes_scratch_new();
+    if (!c->lzo) c->lzo = lzo_scratch_new();
+    if (!c->index) c->index = index_scratch_new();
+    rc = f(err);
+  } catch (const ZcError& e) {
+    return fail(c, e);
+  } catch (const std::bad_alloc&) {
+    return fail(c, ZcError{ZC_ERR_NOMEM, "host allocation failed"});
+  }
+  if (rc != ZC_OK)
+    c->err = std::string(what) + ": " + err;
+  else
+    c->err.clear();
+  return rc;
+}
+
+int zc_index_load(zc_ctx* c, const uint8_t* key, const void* d_files, const uint64_t* file_off,
+                  const uint64_t* file_size, size_t n, zc_index_set** set) {
+  ZC_LOCK(c);
+  std::string err;
+  const int checked = index_validate(key, false, d_files, file_off, file_size, n, set, err);
+  return index_entry(c, "zc_index_load", checked, err, [&](std::string& e) {
+    return index_load(c->index, c->aes, c->lzo, false, key, d_files, file_off, file_size, n, set, c->ev_in, c->stream,
+                      e);
+  });
+}
+
+int zc_index_load_host(zc_ctx* c, const uint8_t* key, const void* files, const uint64_t* file_off,
+                       const uint64_t* file_size, size_t n, zc_index_set** set) {
+  ZC_LOCK(c);
+  std::string err;
+  const int checked = index_validate(key, true, files, file_off, file_size, n, set, err);
+  return index_entry(c, "zc_index_load_host", checked, err, [&](std::string& e) {
+    return index_load(c->index, c->aes, c->lzo, true, key, files, file_off, file_size, n, set, nullptr, c->stream, e);
+  });
+}
+
+int zc_bundle_info_parse(zc_ctx* c, const void* d_plain, const uint64_t* info_off, const uint64_t* info_len,
+                         size_t n, uint8_t* ids, uint32_t* sizes, uint64_t cap, uint64_t* bundle_first,
+                         uint8_t* status, uint64_t* n_records) {
+  ZC_LOCK(c);
+  std::string err;
+  const int checked = info_validate(false, d_plain, info_off, info_len, n, bundle_first, status, n_records, err);
+  return index_entry(c, "zc_bundle_info_parse", checked, err, [&](std::string& e) {
+    return info_parse(c->index, false, d_plain, info_off, info_len, n, ids, sizes, cap, bundle_first, status,
+                      n_records, c->ev_in, c->stream, e);
+  });
+}
+
+int zc_bundle_info_parse_host(zc_ctx* c, const void* plain, const uint64_t* info_off, const uint64_t* info_len,
+                              size_t n, uint8_t* ids, uint32_t* sizes, uint64_t cap, uint64_t* bundle_first,
+                              uint8_t* status, uint64_t* n_records) {
+  ZC_LOCK(c);
+  std::string err;
+  const int checked = info_validate(true, plain, info_off, info_len, n, bundle_first, status, n_records, err);
+  return index_entry(c, "zc_bundle_info_parse_host", checked, err, [&](std::string& e) {
+    return info_parse(c->index, true, plain, info_off, info_len, n, ids, sizes, cap, bundle_first, status, n_records,
+                      nullptr, c->stream, e);
+  });
+}
+
+// the set's calls take no context: their message is the thread's (zc_last_error(NULL))
+
+int zc_index_set_counts(const zc_index_set* set, uint64_t* n_files, uint64_t* n_bundles, uint64_t* n_records) {
+  if (!set) return host_arg_error("zc_index_set_counts: null set");
+  index_set_counts(set, n_files, n_bundles, n_records);
+  return ZC_OK;
+}
+
+int zc_index_set_fetch(const zc_index_set* set, uint8_t* ids, uint32_t* sizes, uint64_t* bundle_first,
+                       uint8_t* bundle_ids, uint64_t* index_first, int32_t* status) {
+  if (!set) return host_arg_error("zc_index_set_fetch: null set");
+  std::string err;
+  const int rc = index_set_fetch(set, ids, sizes, bundle_first, bundle_ids, index_first, status, err);
+  g_host_err = rc != ZC_OK ? "zc_index_set_fetch: " + err : std::string();
+  return rc;
+}
+
+int zc_index_set_device(const zc_index_set* set, const void** d_ids, const void** d_sizes) {
+  if (!set) return host_arg_error("zc_index_set_device: null set");
+  index_set_device(set, d_ids, d_sizes);
+  return ZC_OK;
+}
+
+int zc_index_set_destroy(zc_index_set* set) {
+  if (!set) return host_arg_error("zc_index_set_destroy: null set");
+  index_set_destroy(set);
+  return ZC_OK;
+}
+
+int zc_index_serialize(const uint8_t* ids, const uint32_t* sizes, const uint64_t* bundle_first,
+                       const uint8_t* bundle_ids, uint64_t n_bundles, void* out, uint64_t cap, uint64_t* n_out) {
+  std::string err;
+  int rc;
+  try {
+    rc = index_serialize(ids, sizes, bundle_first, bundle_ids, n_bundles, (uint8_t*)out, cap, n_out, err);
+  } catch (const std::bad_alloc&) {
+    g_host_err = "zc_index_serialize: host allocation failed";
+    return ZC_ERR_NOMEM;
+  }
+  g_host_err = rc != ZC_OK ? "zc_index_serialize: " + err : std::string();
+  return rc;
+}
+
+uint64_t zc_index_file_size(uint64_t body, int keyed) { return keyed ? (16 + body + 4) / 16 * 16 + 16 : body + 4; }
+
+int zc_index_last_stats(const zc_ctx* c, double* decrypt_ms, double* adler_ms, double* frame_ms, double* records_ms,
+                        double* total_ms) {
+  ZC_LOCK(c);
+  if (!c) return host_arg_error("zc_index_last_stats: null context");
+  const IndexTimes t = c->index ? *index_times(c->index) : IndexTimes{};
+  if (decrypt_ms) *decrypt_ms = t.decrypt_ms;
+  if (adler_ms) *adler_ms = t.adler_ms;
+  if (frame_ms) *frame_ms = t.frame_ms;
+  if (records_ms) *records_ms = t.records_ms;
+  if (total_ms) *total_ms = t.total_ms;
   return ZC_OK;
 }
