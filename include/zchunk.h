@@ -57,6 +57,11 @@
  *                          IndexFile::Reader        chunk_index.cc:26-79, index_file.cc:44-76
  *   zc_bundle_info_parse   Message::parse of a bundle file's BundleInfo      bundle.cc:157-218
  *   zc_index_serialize     IndexFile::Writer's messages                     index_file.cc:18-42
+ *   zc_xz_decode           LZMADecoder under Bundle::Reader, many bundles a call
+ *                                                      compression.cc:99-107, bundle.cc:179-216
+ *   zc_device_alloc, zc_device_free, zc_upload
+ *                          no counterpart: device memory for callers that have no HIP binding
+ *                          of their own and keep decoded payloads in HBM
  *   zc_last_error          the DEF_EX exceptions / CHECK aborts of the reference
  *                          (backup_creator.cc:112,165-166, chunk_index.hh:88-89)
  */
@@ -760,6 +765,73 @@ uint64_t zc_index_file_size(uint64_t body, int keyed);
  * scan, write), and the whole call's wall clock. */
 int zc_index_last_stats(const zc_ctx* ctx, double* decrypt_ms, double* adler_ms, double* frame_ms,
                         double* records_ms, double* total_ms);
+
+/* ---- LZMA bundles: xz streams decoded on the device ----
+ * zbackup's default compression method: Bundle::Creator writes a bundle's payload through
+ * lzma_easy_encoder(6, LZMA_CHECK_CRC64) (compression.cc:78-97) and Bundle::Reader decodes the body
+ * zc_bundle_unseal points at (zc_bundle_layout.body_off / body_len) with lzma_stream_decoder
+ * (compression.cc:99-107, bundle.cc:179-216).  zc_xz_decode does that for n bundles in one call,
+ * a wave per bundle (zc_xz_core.h is the decoder), and the payloads land where zc_bundle_scatter,
+ * zc_range_read and zc_chunk_meta_compute read them.
+ *
+ * The decoder reads the complete LZMA2 / LZMA format and checks the container as the xz format asks,
+ * but is narrower than liblzma on purpose: one stream of zero or one block whose only filter is
+ * LZMA2, check id 0 (none), 1 (CRC32) or 4 (CRC64).  More blocks, another filter chain, check id 10
+ * (SHA-256) and a second stream behind stream padding are ZC_XZ_E_UNSUPPORTED; liblzma reads them,
+ * zbackup writes none of them.  liblzma's classes: LZMA_FORMAT_ERROR = E_FORMAT; LZMA_DATA_ERROR =
+ * E_HEADER, E_DATA, E_CHECK; LZMA_BUF_ERROR = E_INPUT, E_OUTPUT (lzma_stream_buffer_decode itself
+ * reports input that ends early as LZMA_DATA_ERROR).
+ * Bytes after the stream's footer are not an error of the decode (liblzma returns LZMA_OK with
+ * in_pos at the stream's end): `consumed` says where it ended, for the caller to compare with the
+ * body's length, where the reference's Adler-32 check would fail.
+ * Callers detect these entry points by their symbols (the ABI version stays 5). */
+enum {
+  ZC_XZ_OK = 0,
+  ZC_XZ_E_FORMAT = 1,      /* not an xz stream */
+  ZC_XZ_E_UNSUPPORTED = 2, /* see above; also reserved bits in the stream or block flags */
+  ZC_XZ_E_HEADER = 3,      /* a CRC32 of header, block header, index or footer is wrong, or block
+                              header, index or footer disagree with the block */
+  ZC_XZ_E_DATA = 4,        /* LZMA2 or LZMA data error, block padding not zero */
+  ZC_XZ_E_INPUT = 5,       /* the stream runs past in_size */
+  ZC_XZ_E_OUTPUT = 6,      /* more output than out_cap: the reference's exTooMuchData */
+  ZC_XZ_E_CHECK = 7,       /* the stored CRC32 / CRC64 does not match the output */
+  ZC_XZ_E_BUDGET = 8       /* the walk's trip count ran out: never, in a correct build */
+};
+typedef struct zc_xz_result {
+  int32_t status;    /* ZC_XZ_* */
+  uint32_t info;     /* bits 0-3: the stream's check id; bit 8: decoded by the wide form */
+  uint64_t decoded;  /* bytes written to the output */
+  uint64_t consumed; /* bytes of input up to and including the stream footer (status 0 only) */
+} zc_xz_result;
+/* LZMADecoder (compression.cc:99-107) under Bundle::Reader (bundle.cc:179-216), for n bundles:
+ * stream i, d_in[in_off[i] ..+ in_size[i]), decodes to d_out + out_off[i], room out_cap[i].
+ * A bad stream does not fail the call: it gets its status.  Nothing outside
+ * [out_off[i], out_off[i] + out_cap[i]) is written; on a status other than ZC_XZ_OK the first
+ * `decoded` bytes of the range are unspecified.  ZC_ERR_ARG with a message, before any device work:
+ * NULL pointers, output ranges that overlap.  No input range may touch an output range.  n == 0 is
+ * ZC_OK and launches nothing.  Runs on the context's stream after the work queued on the default
+ * stream so far, as the other bundle calls do. */
+int zc_xz_decode(zc_ctx* ctx, const void* d_in, const uint64_t* in_off, const uint64_t* in_size, size_t n,
+                 void* d_out, const uint64_t* out_off, const uint64_t* out_cap, zc_xz_result* res);
+/* the same with streams and payloads in host memory (one upload; the decoded bytes are copied back) */
+int zc_xz_decode_host(zc_ctx* ctx, const void* in, const uint64_t* in_off, const uint64_t* in_size, size_t n,
+                      void* out, const uint64_t* out_off, const uint64_t* out_cap, zc_xz_result* res);
+/* The context's last zc_xz_decode: time on the stream of the decode kernels (both forms) and of
+ * the check kernel, the whole call's wall clock, and how many bundles the wide form decoded. */
+int zc_xz_last_stats(const zc_ctx* ctx, double* decode_ms, double* check_ms, double* total_ms, uint64_t* n_wide);
+/* For callers without a HIP binding of their own (the Python wrappers and the adapter's
+ * GpuXzBundleDecoder keep decoded payloads in HBM with these).  They are part of the ABI like
+ * every other entry point (detected by symbol; the ABI version stays 5).
+ * zc_device_alloc: *d_ptr = a buffer of `bytes` bytes (0: a valid pointer to no bytes) on the
+ * context's device; on any failure *d_ptr is NULL (ZC_ERR_NOMEM when the device has no room).
+ * zc_device_free: waits for the work on the context's stream, then frees; NULL is ZC_OK.
+ * zc_upload: n host bytes to device memory on the context's stream, after the work queued on the
+ * default stream so far, complete on return; n == 0 is ZC_OK and touches nothing.
+ * ZC_ERR_ARG with a message (zc_last_error(NULL) without a context): a NULL context, a NULL d_ptr
+ * for zc_device_alloc, a NULL d_dst or host with n > 0. */
+int zc_device_alloc(zc_ctx* ctx, uint64_t bytes, void** d_ptr);
+int zc_device_free(zc_ctx* ctx, void* d_ptr);
+int zc_upload(zc_ctx* ctx, void* d_dst, const void* host, uint64_t n);
 
 int zc_abi_version(void);
 /* digest of the sources this library was built from (zbackup_amd/_build.py

@@ -649,6 +649,159 @@ public:
   }
 };
 
+/// LZMA bundles (the default compression method) decoded on the GPU, behind
+/// GpuBundleUnsealer: the bodies it yields are the xz streams LZMADecoder
+/// (compression.cc:99-107) reads under Bundle::Reader (bundle.cc:179-216), and
+/// BundleInfo gives each payload's size (the sum of its chunk sizes).  decodeAll
+/// returns the payloads as Reader's `payload` strings; decodeToDevice leaves
+/// them in a device buffer, back to back at 16-byte aligned offsets, for
+/// callers that go on with zc_bundle_scatter, zc_range_set_slot or
+/// zc_chunk_meta_compute.  A body that is not exactly its payload -- a stream
+/// error, bytes behind the stream's end (where the reference's Adler-32 check
+/// fails), another size than BundleInfo's -- throws, naming the bundle.
+class GpuXzBundleDecoder: NoCopy
+{
+  ZcContextPool pool;
+
+  static void judge( size_t n, zc_xz_result const * res, std::vector< string const * > const & bodies,
+                     std::vector< uint64_t > const & sizes )
+  {
+    for ( size_t i = 0; i < n; ++i )
+    {
+      char msg[ 160 ];
+      if ( res[ i ].status != ZC_XZ_OK )
+        snprintf( msg, sizeof( msg ), "bundle %zu: xz status %d after %llu bytes", i, (int) res[ i ].status,
+                  (unsigned long long) res[ i ].decoded );
+      else if ( res[ i ].consumed != bodies[ i ]->size() )
+        snprintf( msg, sizeof( msg ), "bundle %zu: the stream ends after %llu of the body's %zu bytes", i,
+                  (unsigned long long) res[ i ].consumed, bodies[ i ]->size() );
+      else if ( res[ i ].decoded != sizes[ i ] )
+        snprintf( msg, sizeof( msg ), "bundle %zu: %llu bytes decoded, its payload has %llu", i,
+                  (unsigned long long) res[ i ].decoded, (unsigned long long) sizes[ i ] );
+      else
+        continue;
+      throw std::runtime_error( msg );
+    }
+  }
+
+  static void layout( std::vector< string const * > const & bodies, std::vector< uint64_t > const & sizes,
+                      string & in, std::vector< uint64_t > & inOff, std::vector< uint64_t > & inSize,
+                      std::vector< uint64_t > & outOff, uint64_t & outBytes )
+  {
+    size_t n = bodies.size();
+    if ( sizes.size() != n )
+      throw std::logic_error( "GpuXzBundleDecoder: bodies and sizes differ in number" );
+    inOff.resize( n );
+    inSize.resize( n );
+    outOff.resize( n );
+    outBytes = 0;
+    for ( size_t i = 0; i < n; ++i )
+    {
+      inOff[ i ] = in.size();
+      inSize[ i ] = bodies[ i ]->size();
+      in += *bodies[ i ];
+      in.resize( ( in.size() + 15 ) / 16 * 16 );
+      outOff[ i ] = outBytes;
+      outBytes += ( sizes[ i ] + 15 ) / 16 * 16;
+    }
+  }
+
+public:
+  /// Payloads in device memory: payload i is `sizes[ i ]` bytes at `data + offsets[ i ]`.
+  /// The buffer belongs to this object and goes with it; it must not outlive
+  /// the decoder that filled it (it holds one of the decoder's contexts).
+  struct DevicePayloads: NoCopy
+  {
+    zc_ctx * ctx;
+    ZcContextPool * pool;
+    char * data;
+    uint64_t bytes;  // the payloads' extent: offsets[ i ] + sizes[ i ] <= bytes
+    std::vector< uint64_t > offsets, sizes;
+    DevicePayloads(): ctx( 0 ), pool( 0 ), data( 0 ), bytes( 0 ) {}
+    ~DevicePayloads()
+    {
+      if ( ctx )
+      {
+        zc_device_free( ctx, data );
+        pool->release( ctx );
+      }
+    }
+  };
+
+  explicit GpuXzBundleDecoder( int device = 0 ): pool( device ) {}
+
+  void decode( string const & body, uint64_t size, string & payload )
+  {
+    std::vector< string const * > b( 1, &body );
+    std::vector< uint64_t > s( 1, size );
+    std::vector< string > out;
+    decodeAll( b, s, out );
+    payload.swap( out[ 0 ] );
+  }
+
+  /// several bundles in one device call, the payloads back on the host
+  void decodeAll( std::vector< string const * > const & bodies, std::vector< uint64_t > const & sizes,
+                  std::vector< string > & payloads )
+  {
+    string in, out;
+    std::vector< uint64_t > inOff, inSize, outOff;
+    uint64_t outBytes;
+    layout( bodies, sizes, in, inOff, inSize, outOff, outBytes );
+    size_t n = bodies.size();
+    std::vector< zc_xz_result > res( n ? n : 1 );
+    if ( in.empty() )
+      in.resize( 16 );
+    out.resize( outBytes ? outBytes : 1 );
+    zc_ctx * ctx = pool.acquire();
+    int rc = zc_xz_decode_host( ctx, in.data(), inOff.data(), inSize.data(), n, &out[ 0 ], outOff.data(),
+                                sizes.data(), res.data() );
+    string err = rc == ZC_OK ? string() : string( zc_last_error( ctx ) );
+    pool.release( ctx );
+    if ( rc != ZC_OK )
+      throw std::runtime_error( err );
+    judge( n, res.data(), bodies, sizes );
+    payloads.resize( n );
+    for ( size_t i = 0; i < n; ++i )
+      payloads[ i ].assign( out, outOff[ i ], sizes[ i ] );
+  }
+
+  /// the same with the payloads left in HBM: only the compressed bodies cross
+  void decodeToDevice( std::vector< string const * > const & bodies, std::vector< uint64_t > const & sizes,
+                       DevicePayloads & dev )
+  {
+    if ( dev.ctx )
+      throw std::logic_error( "GpuXzBundleDecoder: DevicePayloads is in use" );
+    string in;
+    std::vector< uint64_t > inOff, inSize, outOff;
+    uint64_t outBytes;
+    layout( bodies, sizes, in, inOff, inSize, outOff, outBytes );
+    size_t n = bodies.size();
+    std::vector< zc_xz_result > res( n ? n : 1 );
+    zc_ctx * ctx = pool.acquire();
+    void * buf = 0;
+    int rc = zc_device_alloc( ctx, outBytes + in.size(), &buf );
+    if ( rc == ZC_OK )
+      rc = zc_upload( ctx, (char *) buf + outBytes, in.data(), in.size() );
+    if ( rc == ZC_OK )
+      rc = zc_xz_decode( ctx, (char *) buf + outBytes, inOff.data(), inSize.data(), n, buf, outOff.data(),
+                         sizes.data(), res.data() );
+    if ( rc != ZC_OK )
+    {
+      string err = zc_last_error( ctx );
+      zc_device_free( ctx, buf );
+      pool.release( ctx );
+      throw std::runtime_error( err );
+    }
+    dev.ctx = ctx;  // from here on the buffer and the context go with dev
+    dev.pool = &pool;
+    dev.data = (char *) buf;
+    dev.bytes = outBytes;
+    dev.offsets = outOff;
+    dev.sizes = sizes;
+    judge( n, res.data(), bodies, sizes );
+  }
+};
+
 /// Adopting a repository stock zbackup wrote: its chunks are known by id only,
 /// and ids alone go through the exact screen at every byte.  This computes the
 /// chunk metadata (zc_chunk_meta) of every chunk of the bundles handed to it
@@ -680,6 +833,57 @@ private:
   std::vector< Mismatch > bad;
   uint64_t chunks, bytes;
 
+  /// the pending chunks' results into `bad` and `meta`
+  void fold( std::vector< zc_chunk_meta > const & out, std::vector< uint8_t > const & status )
+  {
+    for ( size_t i = 0; i < out.size(); ++i )
+      if ( status[ i ] )
+      {
+        Mismatch m = { bundleOf[ i ], chunkOf[ i ], status[ i ] };
+        bad.push_back( m );
+      }
+      else if ( out[ i ].size == maxSize )
+        meta.push_back( out[ i ] );
+  }
+
+  /// the chunk records of one bundle whose payload starts at `pos` of the
+  /// buffer they will be hashed in; returns the sum of their sizes
+  template< class Info >
+  uint64_t pushRecords( Bundle::Id const & id, Info const & info, uint64_t pos )
+  {
+    uint64_t total = 0;
+    for ( int i = 0; i < info.chunk_record_size(); ++i )
+    {
+      std::string const & blob = info.chunk_record( i ).id();
+      if ( blob.size() != 24 )
+      {
+        popRecords( (size_t)i );
+        throw std::runtime_error( "adopt: a chunk id that is not 24 bytes" );
+      }
+      zc_seed s;
+      memcpy( s.sha1, blob.data(), 16 );
+      memcpy( &s.rolling, blob.data() + 16, 8 );  // ChunkId::setFromBlob, chunk_id.cc:29-38 (little-endian host)
+      s.size = info.chunk_record( i ).size();
+      s.reserved = 0;
+      off.push_back( pos + total );
+      size.push_back( s.size );
+      chunkOf.push_back( (uint32_t)i );
+      expect.push_back( s );
+      bundleOf.push_back( id );
+      total += s.size;
+    }
+    return total;
+  }
+
+  void popRecords( size_t n )
+  {
+    off.resize( off.size() - n );
+    size.resize( size.size() - n );
+    chunkOf.resize( chunkOf.size() - n );
+    expect.resize( expect.size() - n );
+    bundleOf.resize( bundleOf.size() - n );
+  }
+
   void flush()
   {
     if ( off.empty() )
@@ -690,14 +894,7 @@ private:
     zcCheck( zc_chunk_meta_compute_host( ctx, payloads.data(), payloads.size(), off.data(), size.data(), off.size(),
                                          expect.data(), out.data(), status.data(), &nBad ),
              ctx, "zc_chunk_meta_compute_host" );
-    for ( size_t i = 0; i < out.size(); ++i )
-      if ( status[ i ] )
-      {
-        Mismatch m = { bundleOf[ i ], chunkOf[ i ], status[ i ] };
-        bad.push_back( m );
-      }
-      else if ( out[ i ].size == maxSize )
-        meta.push_back( out[ i ] );
+    fold( out, status );
     payloads.clear();
     off.clear();
     size.clear();
@@ -723,32 +920,10 @@ public:
   template< class Info >
   void addBundle( Bundle::Id const & id, Info const & info, std::string const & payload )
   {
-    uint64_t pos = payloads.size(), total = 0;
-    for ( int i = 0; i < info.chunk_record_size(); ++i )
-    {
-      std::string const & blob = info.chunk_record( i ).id();
-      if ( blob.size() != 24 )
-        throw std::runtime_error( "adopt: a chunk id that is not 24 bytes" );
-      zc_seed s;
-      memcpy( s.sha1, blob.data(), 16 );
-      memcpy( &s.rolling, blob.data() + 16, 8 );  // ChunkId::setFromBlob, chunk_id.cc:29-38 (little-endian host)
-      s.size = info.chunk_record( i ).size();
-      s.reserved = 0;
-      off.push_back( pos + total );
-      size.push_back( s.size );
-      chunkOf.push_back( (uint32_t)i );
-      expect.push_back( s );
-      bundleOf.push_back( id );
-      total += s.size;
-    }
+    uint64_t total = pushRecords( id, info, payloads.size() );
     if ( total != payload.size() )
     {
-      size_t n = (size_t)info.chunk_record_size();
-      off.resize( off.size() - n );
-      size.resize( size.size() - n );
-      chunkOf.resize( chunkOf.size() - n );
-      expect.resize( expect.size() - n );
-      bundleOf.resize( bundleOf.size() - n );
+      popRecords( (size_t)info.chunk_record_size() );
       throw std::runtime_error( "adopt: a bundle's payload is not the sum of its chunk sizes" );
     }
     payloads.append( payload );
@@ -756,6 +931,52 @@ public:
     bytes += total;
     if ( payloads.size() >= (size_t)FlushBytes )
       flush();
+  }
+
+  /// Bundles whose payloads GpuXzBundleDecoder::decodeToDevice left in HBM:
+  /// bundle i is ids[ i ] / *infos[ i ] with its payload at dev.data +
+  /// dev.offsets[ i ].  They are hashed where they lie, in one device call;
+  /// nothing of them crosses to the host.  Everything is checked before
+  /// anything is hashed: a refused call leaves nothing behind.
+  template< class Info >
+  void addBundlesDevice( std::vector< Bundle::Id > const & ids, std::vector< Info const * > const & infos,
+                         GpuXzBundleDecoder::DevicePayloads const & dev )
+  {
+    if ( ids.size() != infos.size() || ids.size() != dev.sizes.size() || !dev.ctx )
+      throw std::logic_error( "adopt: ids, infos and device payloads differ in number" );
+    flush();  // the host payloads added before keep their place in the order
+    uint64_t newChunks = 0, newBytes = 0;
+    try
+    {
+      for ( size_t b = 0; b < ids.size(); ++b )
+      {
+        uint64_t total = pushRecords( ids[ b ], *infos[ b ], dev.offsets[ b ] );
+        if ( total != dev.sizes[ b ] )
+          throw std::runtime_error( "adopt: a bundle's payload is not the sum of its chunk sizes" );
+        newChunks += (uint64_t)infos[ b ]->chunk_record_size();
+        newBytes += total;
+      }
+    }
+    catch ( ... )
+    {
+      popRecords( off.size() );  // after the flush above every pending record is this call's
+      throw;
+    }
+    if ( !off.empty() )
+    {
+      std::vector< zc_chunk_meta > out( off.size() );
+      std::vector< uint8_t > status( off.size() );
+      size_t nBad = 0;
+      int rc = zc_chunk_meta_compute( ctx, dev.data, dev.bytes, off.data(), size.data(), off.size(), expect.data(),
+                                      out.data(), status.data(), &nBad );
+      if ( rc != ZC_OK )
+        popRecords( off.size() );
+      zcCheck( rc, ctx, "zc_chunk_meta_compute" );
+      fold( out, status );
+      popRecords( off.size() );
+    }
+    chunks += newChunks;
+    bytes += newBytes;
   }
 
   /// the rest through the GPU, then one sidecar file in metaDir ("" when no
@@ -820,7 +1041,9 @@ private:
   uint64_t budget;
   int64_t totalSize;
   std::vector< size_t > bundleOfSlot;  // slot -> bundle number
+  std::map< size_t, uint32_t > slotOfBundle;
   std::vector< uint64_t > slotSize;
+  std::vector< char > pinned;  // the slot's payload is the caller's device memory (setPayloads): never evicted, outside the budget
   // the cache of resident payloads: saveData is const, as the reference's
   mutable uint64_t residentBytes, tick, fetches, evictions;
   mutable std::vector< uint64_t > lastUse;
@@ -838,7 +1061,7 @@ private:
     {
       size_t victim = resident.size();
       for ( size_t s = 0; s < resident.size(); ++s )
-        if ( resident[ s ] && !wanted[ s ] && ( victim == resident.size() || lastUse[ s ] < lastUse[ victim ] ) )
+        if ( resident[ s ] && !pinned[ s ] && !wanted[ s ] && ( victim == resident.size() || lastUse[ s ] < lastUse[ victim ] ) )
           victim = s;
       if ( victim == resident.size() )
         return;  // only this read's own bundles are left
@@ -862,7 +1085,7 @@ private:
     {
       wanted[ slots[ i ] ] = 1;
       lastUse[ slots[ i ] ] = ++tick;
-      if ( !resident[ slots[ i ] ] )
+      if ( !resident[ slots[ i ] ] && !pinned[ slots[ i ] ] )
         missing += slotSize[ slots[ i ] ];
     }
     evictDownTo( budget > missing ? budget - missing : 0, wanted );
@@ -870,7 +1093,7 @@ private:
     for ( size_t i = 0; i < n; ++i )
     {
       uint32_t s = slots[ i ];
-      if ( resident[ s ] )
+      if ( resident[ s ] || pinned[ s ] )
         continue;
       source.getPayload( bundleOfSlot[ s ], payload );
       if ( payload.size() != slotSize[ s ] )
@@ -910,7 +1133,6 @@ public:
     check( zc_parse_instructions( backupData.data(), backupData.size(), ins.data(), ins.size(), &count ),
            "zc_parse_instructions" );
     // slots: the bundles the stream names, in first-use order, then the instruction stream
-    std::map< size_t, uint32_t > slotOfBundle;
     std::vector< uint32_t > slot( count );
     std::vector< uint64_t > off( count ), size( count );
     for ( size_t e = 0; e < count; ++e )
@@ -959,6 +1181,52 @@ public:
     slotSize.pop_back();  // the instruction stream stays resident and outside the budget
     resident.assign( slotSize.size(), 0 );
     lastUse.assign( slotSize.size(), 0 );
+    pinned.assign( slotSize.size(), 0 );
+  }
+
+  /// Payloads GpuXzBundleDecoder::decodeToDevice left in HBM become the slots
+  /// of their bundles: payload i of `dev` is bundle number bundleNumbers[ i ] of
+  /// the list given at construction.  Reads are served from them where they
+  /// lie; they are never evicted and do not count against the budget, and the
+  /// source is not asked for these bundles.  A bundle the backup does not name
+  /// is skipped.  `dev` must stay alive until clearPayloads() or this object's
+  /// end; a size that is not the bundle's throws before any slot changes.
+  void setPayloads( std::vector< size_t > const & bundleNumbers, GpuXzBundleDecoder::DevicePayloads const & dev )
+  {
+    if ( bundleNumbers.size() != dev.sizes.size() || !dev.ctx )
+      throw std::logic_error( "IndexedRestorer: bundle numbers and device payloads differ in number" );
+    std::vector< std::pair< uint32_t, size_t > > todo;  // ( slot, payload in dev )
+    for ( size_t i = 0; i < bundleNumbers.size(); ++i )
+    {
+      std::map< size_t, uint32_t >::const_iterator it = slotOfBundle.find( bundleNumbers[ i ] );
+      if ( it == slotOfBundle.end() )
+        continue;
+      if ( dev.sizes[ i ] != slotSize[ it->second ] )
+        throw std::runtime_error( "IndexedRestorer: a bundle's payload is not the sum of its chunk sizes" );
+      todo.push_back( std::make_pair( it->second, i ) );
+    }
+    for ( size_t k = 0; k < todo.size(); ++k )
+    {
+      uint32_t s = todo[ k ].first;
+      check( zc_range_set_slot( index, s, dev.data + dev.offsets[ todo[ k ].second ] ), "zc_range_set_slot" );
+      if ( resident[ s ] )  // an uploaded copy went with the call above
+      {
+        resident[ s ] = 0;
+        residentBytes -= slotSize[ s ];
+      }
+      pinned[ s ] = 1;
+    }
+  }
+
+  /// the slots set by setPayloads are empty again (before their device memory goes)
+  void clearPayloads()
+  {
+    for ( size_t s = 0; s < pinned.size(); ++s )
+      if ( pinned[ s ] )
+      {
+        check( zc_range_set_slot( index, (uint32_t)s, 0 ), "zc_range_set_slot" );
+        pinned[ s ] = 0;
+      }
   }
 
   ~GpuIndexedRestorer()

@@ -45,6 +45,12 @@ def bundle_layout(bundles, payloads):
     is not the sum of its chunk sizes."""
     if len(bundles) != len(payloads):
         raise _lib.ZcError(f"adopt: {len(bundles)} bundles, {len(payloads)} payloads")
+    return chunk_layout(bundles, [len(p) for p in payloads])
+
+
+def chunk_layout(bundles, payload_sizes=None):
+    """bundle_layout from sizes alone: payload_sizes[b] = the bytes of bundle
+    b's payload (None: whatever its chunks take)."""
     n = sum(len(b) for b in bundles)
     off, size = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint32)
     expect = np.zeros(n, dtype=SEED_DTYPE)
@@ -61,8 +67,8 @@ def bundle_layout(bundles, payloads):
             expect["size"][i] = int(sz)
             total += int(sz)
             i += 1
-        if len(payloads[b]) != total:
-            raise _lib.ZcError(f"adopt: bundle {b} decoded to {len(payloads[b])} bytes, its chunks take {total}")
+        if payload_sizes is not None and payload_sizes[b] != total:
+            raise _lib.ZcError(f"adopt: bundle {b} decoded to {payload_sizes[b]} bytes, its chunks take {total}")
         pos += total
         bundle_first.append(i)
     return off, size, expect, bundle_first
@@ -98,6 +104,7 @@ class Adopter:
         self._ctx = ctx
         self._call_ms = 0.0
         self.n_bad = 0
+        self.xz_stats = None  # BundleDecompressor.last_stats() of the last adopt_bodies
 
     def _run(self, fn, what, payload, payload_bytes, off, size, expect):
         off = np.ascontiguousarray(off, dtype=np.uint64)
@@ -145,6 +152,29 @@ class Adopter:
         meta, status = self._run(self._L.zc_chunk_meta_compute_host, "zc_chunk_meta_compute_host",
                                  ctypes.c_void_p(image.ctypes.data), int(size.astype(np.uint64).sum()), off, size,
                                  expect)
+        return build_report(bundle_first, meta, status, self.chunk_max_size)
+
+    def adopt_bodies(self, bundles, bodies):
+        """adopt() for LZMA bundles as they lie on disk: bodies[b] = bundle b's
+        xz stream (zc_bundle_unseal's body).  The compressed bodies cross to the
+        device, are decoded there back to back (zc_xz_decode; a stream that is
+        not exactly its bundle's payload raises ZcError naming the bundle) and
+        hashed where they land: the payloads never touch the host."""
+        from .bundle import BundleDecompressor
+        totals = [sum(int(s) for _, s in chunks) for chunks in bundles]
+        off, size, expect, bundle_first = chunk_layout(bundles)
+        if len(bodies) != len(bundles):
+            raise _lib.ZcError(f"adopt: {len(bundles)} bundles, {len(bodies)} bodies")
+        dec = BundleDecompressor(ctx=self._ctx)
+        pay = (sum(totals) + 15) & ~15
+        buf = dec.alloc(pay + dec.stage_size(bodies))
+        try:
+            out_off = np.concatenate([[0], np.cumsum(totals)[:-1]]).astype(np.uint64) if totals else []
+            dec.decode_bodies(bodies, buf + pay, buf, out_off, totals)
+            self.xz_stats = dec.last_stats()
+            meta, status = self.chunk_meta(buf, sum(totals), off, size, expect)
+        finally:
+            dec.free(buf)
         return build_report(bundle_first, meta, status, self.chunk_max_size)
 
     def last_stats(self):

@@ -15,6 +15,10 @@ file EncryptedFile::OutputStream writes and InputStream reads back
 (encrypted_file.cc:20-392, bundle.cc:96-218), `aes_encrypt` / `aes_decrypt`
 the AES-128-CBC under them (encryption.cc:17-95).
 
+For LZMA bundles (the default compression method): `BundleDecompressor` is
+Bundle::Reader's lzma_stream_decoder (compression.cc:99-107, bundle.cc:179-216)
+for many bundles in one device call (zc_xz_decode).
+
 `plan_bundles` is host bookkeeping; `BundleCompressor.gather` and `.compress`
 run on the GPU through libzchunk.so (zc_bundle_gather / zc_lzo_compress);
 there is no CPU fallback.  Device buffers are passed as raw pointers (e.g. a
@@ -273,6 +277,144 @@ class BundleCompressor:
         ms, blocks = ctypes.c_double(), ctypes.c_uint64()
         self._L.zc_lzo_last_stats(self._ctx, ctypes.byref(ms), ctypes.byref(blocks))
         return ms.value, blocks.value
+
+    def close(self):
+        if self._own and self._ctx:
+            self._L.zc_destroy(self._ctx)
+        self._ctx = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+XZ_RESULT_DTYPE = np.dtype([("status", "<i4"), ("info", "<u4"), ("decoded", "<u8"), ("consumed", "<u8")])
+assert XZ_RESULT_DTYPE.itemsize == ctypes.sizeof(_lib.ZcXzResult)
+
+
+class BundleDecompressor:
+    """LZMA bundles decoded on the GPU (zc_xz_decode): Bundle::Reader's
+    lzma_stream_decoder (compression.cc:99-107, bundle.cc:179-216) for many
+    bundles in one call, on a context of its own or on another object's
+    (`ctx=bc._ctx`).  There is no CPU fallback."""
+
+    def __init__(self, device=0, ctx=None):
+        self._L = _lib.load()
+        self._own = ctx is None
+        if ctx is None:
+            ctx = ctypes.c_void_p()
+            rc = self._L.zc_create(ctypes.byref(ctx), 65536, device, 0)
+            if rc != _lib.ZC_OK:
+                raise _lib.ZcError(f"zc_create failed ({rc})")
+        self._ctx = ctx
+
+    @staticmethod
+    def _judge(res, in_size, sizes):
+        """The strictness of Bundle::Reader: the stream good, the whole body
+        used (where the reference's Adler-32 would fail otherwise), the
+        payload of BundleInfo's size."""
+        for k, r in enumerate(res):
+            st = int(r["status"])
+            if st != _lib.ZC_XZ_OK:
+                raise _lib.ZcError(f"bundle {k}: {_lib.XZ_STATUS_NAMES.get(st, st)} (status {st}) after "
+                                   f"{int(r['decoded'])} bytes")
+            if int(r["consumed"]) != int(in_size[k]):
+                raise _lib.ZcError(f"bundle {k}: the stream ends after {int(r['consumed'])} of the body's "
+                                   f"{int(in_size[k])} bytes")
+            if sizes is not None and int(r["decoded"]) != int(sizes[k]):
+                raise _lib.ZcError(f"bundle {k}: {int(r['decoded'])} bytes decoded, its payload has {int(sizes[k])}")
+
+    def decode(self, d_in, in_off, in_size, d_out, out_off, out_cap, strict=True):
+        """Stream i, d_in[in_off[i] ..+ in_size[i]), to d_out + out_off[i] with
+        room out_cap[i] = the payload's size.  Returns an XZ_RESULT_DTYPE
+        array; raises ZcError naming the first bundle that is not exactly its
+        payload (strict=False: the statuses are the caller's to read)."""
+        in_off, in_size, out_off, out_cap = _u64(in_off), _u64(in_size), _u64(out_off), _u64(out_cap)
+        if not len(in_off) == len(in_size) == len(out_off) == len(out_cap):
+            raise ValueError("decode: in_off, in_size, out_off and out_cap differ in length")
+        res = np.zeros(len(in_off), dtype=XZ_RESULT_DTYPE)
+        rc = self._L.zc_xz_decode(self._ctx, d_in, in_off.ctypes.data, in_size.ctypes.data, len(in_off), d_out,
+                                  out_off.ctypes.data, out_cap.ctypes.data, res.ctypes.data)
+        _check(self._L, self._ctx, rc, "zc_xz_decode")
+        if strict:
+            self._judge(res, in_size, out_cap)
+        return res
+
+    def decode_host(self, bodies, sizes, strict=True):
+        """Host bytes in, payload bytes out (zc_xz_decode_host), one call for
+        all; sizes[i] = the payload's size from BundleInfo."""
+        bodies = [bytes(b) for b in bodies]
+        if len(bodies) != len(sizes):
+            raise ValueError("decode_host: bodies and sizes differ in length")
+        in_size = np.array([len(b) for b in bodies], dtype=np.uint64)
+        in_off = np.concatenate([[0], np.cumsum(in_size)[:-1]]).astype(np.uint64) if len(bodies) else in_size
+        cap = _u64([int(s) for s in sizes])
+        out_off = np.concatenate([[0], np.cumsum(cap)[:-1]]).astype(np.uint64) if len(cap) else cap
+        src = np.frombuffer(b"".join(bodies) or b"\0", dtype=np.uint8)
+        out = np.zeros(int(cap.sum()) or 1, dtype=np.uint8)
+        res = np.zeros(len(bodies), dtype=XZ_RESULT_DTYPE)
+        rc = self._L.zc_xz_decode_host(self._ctx, src.ctypes.data, in_off.ctypes.data, in_size.ctypes.data,
+                                       len(bodies), out.ctypes.data, out_off.ctypes.data, cap.ctypes.data,
+                                       res.ctypes.data)
+        _check(self._L, self._ctx, rc, "zc_xz_decode_host")
+        if strict:
+            self._judge(res, in_size, cap)
+            return [out[int(o):int(o) + int(s)].tobytes() for o, s in zip(out_off, cap)]
+        return [out[int(o):int(o) + int(r["decoded"])].tobytes() if r["status"] == 0 else int(r["status"])
+                for o, r in zip(out_off, res)], res
+
+    # ---- host bodies in, payloads kept in HBM ----
+
+    @staticmethod
+    def stage_size(bodies):
+        """Device bytes the bodies take when staged (each 16-byte aligned)."""
+        return sum((len(b) + 15) & ~15 for b in bodies)
+
+    def alloc(self, n):
+        """A device buffer of n bytes on the context's device (free() it)."""
+        p = ctypes.c_void_p()
+        _check(self._L, self._ctx, self._L.zc_device_alloc(self._ctx, int(n), ctypes.byref(p)), "zc_device_alloc")
+        return p.value
+
+    def free(self, d_ptr):
+        _check(self._L, self._ctx, self._L.zc_device_free(self._ctx, d_ptr), "zc_device_free")
+
+    def upload(self, d_dst, data):
+        buf = np.ascontiguousarray(np.frombuffer(memoryview(data), dtype=np.uint8))
+        if buf.size:
+            _check(self._L, self._ctx, self._L.zc_upload(self._ctx, d_dst, buf.ctypes.data, buf.size), "zc_upload")
+
+    def decode_bodies(self, bodies, d_stage, d_out, out_off, sizes):
+        """The compressed bodies (host bytes) cross to d_stage (stage_size(bodies)
+        bytes of device memory) in one upload and decode to d_out + out_off[i];
+        the payloads never touch the host.  Strict, as decode()."""
+        bodies = [bytes(b) for b in bodies]
+        in_size = [len(b) for b in bodies]
+        in_off, pos = [], 0
+        for n in in_size:
+            in_off.append(pos)
+            pos += (n + 15) & ~15
+        img = np.zeros(max(pos, 1), dtype=np.uint8)
+        for o, b in zip(in_off, bodies):
+            img[o:o + len(b)] = np.frombuffer(b, dtype=np.uint8)
+        if pos:
+            self.upload(d_stage, img[:pos])
+        return self.decode(d_stage, in_off, in_size, d_out, out_off, sizes)
+
+    def last_stats(self):
+        """dict(decode_ms, check_ms, total_ms, n_wide) of the last decode."""
+        d, c, t, w = ctypes.c_double(), ctypes.c_double(), ctypes.c_double(), ctypes.c_uint64()
+        rc = self._L.zc_xz_last_stats(self._ctx, ctypes.byref(d), ctypes.byref(c), ctypes.byref(t), ctypes.byref(w))
+        _check(self._L, self._ctx, rc, "zc_xz_last_stats")
+        return dict(decode_ms=d.value, check_ms=c.value, total_ms=t.value, n_wide=w.value)
 
     def close(self):
         if self._own and self._ctx:

@@ -629,4 +629,23 @@ int index_serialize(const uint8_t* ids, const uint32_t* sizes, const uint64_t* b
                     const uint8_t* bundle_ids, uint64_t n_bundles, uint8_t* out, uint64_t cap, uint64_t* n_out,
                     std::string& err);
 
+// zc_xz.hip: LZMA bundles, xz streams decoded to their payloads (zc_xz_core.h).
+// xz_validate checks what the host can see (no device, no context); xz_decode
+// returns a zc_status with its message in `err`.
+struct XzScratch;
+struct XzTimes {
+  double decode_ms, check_ms, total_ms;  // the decode kernels (both forms), the check kernel, the call's wall clock
+  uint64_t n_wide;                       // bundles the wide form decoded
+};
+XzScratch* xz_scratch_new();
+void xz_scratch_free(XzScratch* s);
+const XzTimes* xz_times(const XzScratch* s);
+int xz_validate(const void* in, const uint64_t* in_off, const uint64_t* in_size, size_t n, const void* out,
+                const uint64_t* out_off, const uint64_t* out_cap, const zc_xz_result* res, std::string& err);
+// host: streams and payloads are in host memory (one upload, the decoded bytes
+// copied back); else ev_in orders the context stream after the legacy default stream
+int xz_decode(XzScratch* s, bool host, const void* in, const uint64_t* in_off, const uint64_t* in_size, size_t n,
+              void* out, const uint64_t* out_off, const uint64_t* out_cap, zc_xz_result* res, hipEvent_t ev_in,
+              hipStream_t st, std::string& err);
+
 }  // namespace zc

@@ -543,6 +543,7 @@ struct zc_ctx {
   MetaScratch* meta = nullptr;  // adoption's buffers (zc_meta.hip), made on first use
   RangeScratch* range = nullptr;  // random-access restore's buffers (zc_range.hip), made on first use
   IndexScratch* index = nullptr;  // index files' buffers (zc_index.hip), made on first use
+  XzScratch* xz = nullptr;        // LZMA bundles' buffers (zc_xz.hip), made on first use
 
   // scratch
   DevBuf<uint64_t> hm_key, hm_fp, hm_rkey;  // metadata of chunks joining the historic index
@@ -3367,6 +3368,7 @@ int zc_destroy(zc_ctx* c) {
     meta_scratch_free(c->meta);
     range_scratch_free(c->range);
     index_scratch_free(c->index);
+    xz_scratch_free(c->xz);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     if (prev >= 0) (void)hipSetDevice(prev);
@@ -4701,5 +4703,107 @@ int zc_index_last_stats(const zc_ctx* c, double* decrypt_ms, double* adler_ms, d
   if (frame_ms) *frame_ms = t.frame_ms;
   if (records_ms) *records_ms = t.records_ms;
   if (total_ms) *total_ms = t.total_ms;
+  return ZC_OK;
+}
+
+// ---- LZMA bundles: xz streams to payloads (zc_xz.hip) ----
+
+static int xz_entry(zc_ctx* c, const char* what, bool host, const void* in, const uint64_t* in_off,
+                    const uint64_t* in_size, size_t n, void* out, const uint64_t* out_off, const uint64_t* out_cap,
+                    zc_xz_result* res) {
+  std::string err;
+  if (!c) return ctx_arg_error(c, (std::string(what) + ": null context").c_str());
+  int rc;
+  try {
+    rc = xz_validate(in, in_off, in_size, n, out, out_off, out_cap, res, err);
+    if (rc != ZC_OK) return ctx_arg_error(c, (std::string(what) + ": " + err).c_str());
+    DeviceGuard g(c->device);
+    if (!c->xz) c->xz = xz_scratch_new();
+    rc = xz_decode(c->xz, host, in, in_off, in_size, n, out, out_off, out_cap, res, host ? nullptr : c->ev_in,
+                   c->stream, err);
+  } catch (const ZcError& e) {
+    return fail(c, e);
+  } catch (const std::bad_alloc&) {
+    return fail(c, ZcError{ZC_ERR_NOMEM, "host allocation failed"});
+  }
+  if (rc != ZC_OK)
+    c->err = std::string(what) + ": " + err;
+  else
+    c->err.clear();
+  return rc;
+}
+
+int zc_xz_decode(zc_ctx* c, const void* d_in, const uint64_t* in_off, const uint64_t* in_size, size_t n, void* d_out,
+                 const uint64_t* out_off, const uint64_t* out_cap, zc_xz_result* res) {
+  ZC_LOCK(c);
+  return xz_entry(c, "zc_xz_decode", false, d_in, in_off, in_size, n, d_out, out_off, out_cap, res);
+}
+
+int zc_xz_decode_host(zc_ctx* c, const void* in, const uint64_t* in_off, const uint64_t* in_size, size_t n, void* out,
+                      const uint64_t* out_off, const uint64_t* out_cap, zc_xz_result* res) {
+  ZC_LOCK(c);
+  return xz_entry(c, "zc_xz_decode_host", true, in, in_off, in_size, n, out, out_off, out_cap, res);
+}
+
+// device memory for callers without a HIP binding of their own (the Python
+// wrappers): a buffer on the context's device, and host bytes into it on the
+// context's stream
+
+int zc_device_alloc(zc_ctx* c, uint64_t bytes, void** d_ptr) {
+  ZC_LOCK(c);
+  if (!c || !d_ptr) return ctx_arg_error(c, "zc_device_alloc: null pointer");
+  *d_ptr = nullptr;
+  DeviceGuard g(c->device);
+  const hipError_t e = hipMalloc(d_ptr, bytes ? bytes : 1);
+  if (e != hipSuccess) {
+    *d_ptr = nullptr;
+    c->err = std::string("zc_device_alloc: ") + hipGetErrorString(e);
+    return e == hipErrorOutOfMemory ? ZC_ERR_NOMEM : ZC_ERR_HIP;
+  }
+  c->err.clear();
+  return ZC_OK;
+}
+
+int zc_device_free(zc_ctx* c, void* d_ptr) {
+  ZC_LOCK(c);
+  if (!c) return ctx_arg_error(c, "zc_device_free: null context");
+  if (!d_ptr) return ZC_OK;
+  DeviceGuard g(c->device);
+  hipError_t e = hipStreamSynchronize(c->stream);  // nothing queued still reads it
+  if (e == hipSuccess) e = hipFree(d_ptr);
+  if (e != hipSuccess) {
+    c->err = std::string("zc_device_free: ") + hipGetErrorString(e);
+    return ZC_ERR_HIP;
+  }
+  c->err.clear();
+  return ZC_OK;
+}
+
+int zc_upload(zc_ctx* c, void* d_dst, const void* host, uint64_t n) {
+  ZC_LOCK(c);
+  if (!c) return ctx_arg_error(c, "zc_upload: null context");
+  if (!n) return ZC_OK;
+  if (!d_dst || !host) return ctx_arg_error(c, "zc_upload: null pointer");
+  DeviceGuard g(c->device);
+  hipError_t e = hipEventRecord(c->ev_in, nullptr);  // after the caller's default-stream work
+  if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, c->ev_in, 0);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_dst, host, n, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) {
+    c->err = std::string("zc_upload: ") + hipGetErrorString(e);
+    return ZC_ERR_HIP;
+  }
+  c->err.clear();
+  return ZC_OK;
+}
+
+int zc_xz_last_stats(const zc_ctx* c, double* decode_ms, double* check_ms, double* total_ms, uint64_t* n_wide) {
+  ZC_LOCK(c);
+  if (!c) return host_arg_error("zc_xz_last_stats: null context");
+  const XzTimes t = c->xz ? *xz_times(c->xz) : XzTimes{};
+  if (decode_ms) *decode_ms = t.decode_ms;
+  if (check_ms) *check_ms = t.check_ms;
+  if (total_ms) *total_ms = t.total_ms;
+  if (n_wide) *n_wide = t.n_wide;
   return ZC_OK;
 }

@@ -14,6 +14,9 @@ lzo1x_decompress_safe, as the reference calls it, compression.cc:472-490;
 `bundle.frame_info` reads the frame): the instruction stream travels to the
 device in the same buffer, so there is one upload (`RestorePlan.host_image`;
 `RestorePlan.instruction_image` is the instruction stream's share of it alone).
+LZMA bundles, zbackup's default, need no host decoder: `Restorer.replay_bodies`
+takes their xz bodies and decodes them into the scratch buffer on the device
+(zc_xz_decode), as `IndexedRestorer.decode_payload` does for one slot.
 
   IndexedRestorer::saveData  -> any byte range            backup_restorer.cc:182-316
 
@@ -27,7 +30,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from .bundle import BundleCompressor, _u64, parse_backup_data
+from .bundle import BundleCompressor, BundleDecompressor, _u64, parse_backup_data
 
 
 def chunk_map(bundles):
@@ -79,6 +82,12 @@ class RestorePlan:
         the payloads are put at pay_off[k] on the device; host_image() is
         this plus the payloads."""
         return self.instr_off, np.frombuffer(self.data, dtype=np.uint8)
+
+    def bodies_work_size(self, bodies):
+        """The scratch buffer's size when the bundles' compressed bodies are
+        decoded on the device (Restorer.replay_bodies): work_size plus the
+        bodies, each 16-byte aligned."""
+        return ((self.work_size + 15) & ~15) + BundleDecompressor.stage_size(bodies)
 
 
 class Restorer:
@@ -136,6 +145,25 @@ class Restorer:
         if keep.any():
             self._comp.scatter(d_work, plan.src_off[keep], plan.sizes[keep], d_out, plan.dst_off[keep])
         return plan.length
+
+    def replay_bodies(self, plan, bodies, d_work, d_out, out_cap):
+        """The same from LZMA bundles as they lie on disk: bodies[k] = the xz
+        stream of bundle plan.used[k] (zc_bundle_unseal's body).  The
+        instruction stream and the compressed bodies go to d_work (device
+        memory of plan.bodies_work_size(bodies) bytes), body k is decoded on
+        the device to d_work + plan.pay_off[k] (zc_xz_decode; a stream that is
+        not exactly its payload raises ZcError naming the bundle), then
+        replay().  The decoded payloads never touch the host."""
+        if len(bodies) != len(plan.used):
+            raise _lib.ZcError(f"restore: {len(bodies)} bodies for {len(plan.used)} referenced bundles")
+        if plan.length > out_cap:
+            raise _lib.ZcError(f"restore: {plan.length} bytes to restore, room for {out_cap}")
+        dec = BundleDecompressor(ctx=self._comp._ctx)
+        off, img = plan.instruction_image()
+        dec.upload(d_work + off, img)
+        stage = (plan.work_size + 15) & ~15
+        dec.decode_bodies(bodies, d_work + stage, d_work, plan.pay_off, plan.pay_size)
+        return self.replay(plan, d_work, d_out, out_cap)
 
     def close(self):
         self._comp.close()
@@ -265,6 +293,7 @@ class IndexedRestorer:
         k[in_instr] = len(plan.used)
         base = np.concatenate([pay_off, [plan.instr_off]]).astype(np.uint64)
         self._slot_of = {b: i for i, b in enumerate(plan.used)}
+        self._decoded = {}  # slot -> device buffer of a payload decoded here
         self._index = None
         try:
             self._index = RangeIndex(list(plan.pay_size) + [len(plan.data)], k, plan.src_off - base[k], plan.sizes,
@@ -287,13 +316,46 @@ class IndexedRestorer:
 
     def set_payload(self, bundle, d_ptr):
         """The bundle's decoded payload in caller-owned device memory."""
-        self._index.set_slot(self._slot(bundle), d_ptr)
+        slot = self._slot(bundle)
+        self._index.set_slot(slot, d_ptr)
+        self._free_decoded(slot)
 
     def upload_payload(self, bundle, payload):
-        self._index.upload_slot(self._slot(bundle), payload)
+        slot = self._slot(bundle)
+        self._index.upload_slot(slot, payload)
+        self._free_decoded(slot)
+
+    def _free_decoded(self, slot):
+        old = self._decoded.pop(slot, None)
+        if old is not None:
+            BundleDecompressor(ctx=self._comp._ctx).free(old)
+
+    def decode_payload(self, bundle, body):
+        """The bundle's payload from its LZMA body (host bytes: the xz stream),
+        decoded on the device into a buffer this object owns, beside
+        upload_payload: the compressed bytes cross, the payload does not."""
+        slot = self._slot(bundle)
+        if self._comp is None:
+            raise _lib.ZcError("decode_payload: a host-only IndexedRestorer has no device")
+        dec = BundleDecompressor(ctx=self._comp._ctx)
+        size = int(self.plan.pay_size[slot])
+        out_bytes = (size + 15) & ~15
+        buf = dec.alloc(out_bytes + dec.stage_size([body]))
+        try:
+            dec.decode_bodies([body], buf + out_bytes, buf, [0], [size])
+            self._index.set_slot(slot, buf)
+        except Exception:
+            dec.free(buf)
+            raise
+        old = self._decoded.pop(slot, None)
+        self._decoded[slot] = buf
+        if old is not None:
+            dec.free(old)
 
     def drop_payload(self, bundle):
-        self._index.drop_slot(self._slot(bundle))
+        slot = self._slot(bundle)
+        self._index.drop_slot(slot)
+        self._free_decoded(slot)
 
     def read(self, reads, d_out, dst_off):
         self._index.read(reads, d_out, dst_off)
@@ -307,8 +369,13 @@ class IndexedRestorer:
     def close(self):
         if self._index is not None:
             self._index.close()
+            self._index = None
         if self._comp is not None:
+            for buf in self._decoded.values():
+                BundleDecompressor(ctx=self._comp._ctx).free(buf)
+            self._decoded = {}
             self._comp.close()
+            self._comp = None
 
     def __enter__(self):
         return self
