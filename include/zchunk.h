@@ -58,6 +58,7 @@
  *   zc_bundle_info_parse   Message::parse of a bundle file's BundleInfo      bundle.cc:157-218
  *   zc_index_serialize     IndexFile::Writer's messages                     index_file.cc:18-42
  *   zc_xz_decode           LZMADecoder under Bundle::Reader, many bundles a call
+ *   zc_xz_encode           LZMAEncoder under Bundle::Creator, many bundles a call
  *                                                      compression.cc:99-107, bundle.cc:179-216
  *   zc_device_alloc, zc_device_free, zc_upload
  *                          no counterpart: device memory for callers that have no HIP binding
@@ -832,6 +833,41 @@ int zc_xz_last_stats(const zc_ctx* ctx, double* decode_ms, double* check_ms, dou
 int zc_device_alloc(zc_ctx* ctx, uint64_t bytes, void** d_ptr);
 int zc_device_free(zc_ctx* ctx, void* d_ptr);
 int zc_upload(zc_ctx* ctx, void* d_dst, const void* host, uint64_t n);
+
+/* ---- LZMA bundles: xz streams encoded on the device ----
+ * The write side of the above: Bundle::Creator's lzma_easy_encoder(6, LZMA_CHECK_CRC64)
+ * (compression.cc:78-97) for n bundles in one call (zc_xzenc_core.h is the encoder).  An xz stream is
+ * defined by its decoder: the streams are not liblzma's bytes, they are streams lzma_stream_decoder
+ * and zc_xz_decode read back to the payload -- one block, LZMA2 alone, lc=3 lp=0 pb=2, the smallest
+ * dictionary size that covers the payload, a greedy parse over hash-table candidates.  The bytes
+ * are a function of the payload and the check id alone (not of the batch, the grid or the room).
+ * Callers detect these entry points by their symbols (the ABI version stays 5). */
+/* Room that always suffices: the stream with every LZMA2 chunk stored (container + 3 bytes per
+ * 64 KiB + payload); the encoder never writes more.  32 for an empty payload. */
+uint64_t zc_xz_capacity(uint64_t payload_size);
+typedef struct zc_xz_enc_result {
+  int32_t status; /* ZC_XZ_OK, or ZC_XZ_E_OUTPUT: out_cap[i] is too small */
+  uint32_t info;  /* bits 0-3: the check id; from bit 8: the count of LZMA2 chunks written stored */
+  uint64_t size;  /* the stream's length (status 0 only) */
+} zc_xz_enc_result;
+/* Payload i, d_payload[pay_off[i] ..+ pay_size[i]), as an xz stream at d_out + out_off[i], room
+ * out_cap[i]; check = 0 (none), 1 (CRC32) or 4 (CRC64, what zbackup writes).  Nothing outside
+ * [out_off[i], out_off[i] + out_cap[i]) is written; with out_cap[i] >= zc_xz_capacity(pay_size[i])
+ * the status is ZC_XZ_OK; on ZC_XZ_E_OUTPUT the range's bytes are unspecified.  ZC_ERR_ARG with a
+ * message, before any device work: NULL pointers, another check id, output ranges that overlap
+ * each other or touch a payload, a payload of more than 64 MiB.  n == 0 is ZC_OK and launches
+ * nothing.  Runs on the context's stream after the work queued on the default stream so far. */
+int zc_xz_encode(zc_ctx* ctx, const void* d_payload, const uint64_t* pay_off, const uint64_t* pay_size, size_t n,
+                 void* d_out, const uint64_t* out_off, const uint64_t* out_cap, uint32_t check,
+                 zc_xz_enc_result* res);
+/* the same with payloads and streams in host memory (one upload; the streams are copied back) */
+int zc_xz_encode_host(zc_ctx* ctx, const void* payload, const uint64_t* pay_off, const uint64_t* pay_size, size_t n,
+                      void* out, const uint64_t* out_off, const uint64_t* out_cap, uint32_t check,
+                      zc_xz_enc_result* res);
+/* The context's last zc_xz_encode: time on the stream of the match kernel, the coding kernel and
+ * the check kernel (summed over the call's batches), and the whole call's wall clock. */
+int zc_xz_encode_last_stats(const zc_ctx* ctx, double* match_ms, double* code_ms, double* check_ms,
+                            double* total_ms);
 
 int zc_abi_version(void);
 /* digest of the sources this library was built from (zbackup_amd/_build.py

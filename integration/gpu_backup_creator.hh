@@ -802,6 +802,82 @@ public:
   }
 };
 
+/// LZMA bundles (the default compression method) written on the GPU: the
+/// counterpart of GpuLzoBundleCompressor for compression_method == "lzma", with
+/// the same interface.  Bundle::Creator::write (bundle.cc:96-155) hands its
+/// payload to LZMAEncoder (compression.cc:78-97); with this class that becomes
+///
+///   string body;
+///   gpuXz.compress( payload, body );    // one payload, or compressAll for a batch
+///   os.write( body.data(), body.size() );
+///
+/// The body is an xz stream (one block, LZMA2, CRC64) that lzma_stream_decoder
+/// and GpuXzBundleDecoder read back to the payload; it is not liblzma's bytes
+/// (another match finder and parse), and it is a function of the payload alone.
+/// A batch pays: the device codes a bundle per wave, some two thousand at once.
+/// Contexts come from a pool, as GpuLzoBundleCompressor's do, so compressor
+/// threads may call at the same time.
+class GpuXzBundleCompressor: NoCopy
+{
+  ZcContextPool pool;
+  uint32_t check;
+
+public:
+  /// check: 4 (CRC64, what zbackup writes), 1 (CRC32) or 0 (none)
+  explicit GpuXzBundleCompressor( int device = 0, uint32_t check_ = 4 ): pool( device ), check( check_ ) {}
+
+  void compress( string const & payload, string & body )
+  {
+    std::vector< string const * > one( 1, &payload );
+    std::vector< string > out;
+    compressAll( one, out );
+    body.swap( out[ 0 ] );
+  }
+
+  /// several finished bundles in one device call
+  void compressAll( std::vector< string const * > const & payloads, std::vector< string > & bodies )
+  {
+    size_t n = payloads.size();
+    std::vector< uint64_t > payOff( n ), paySize( n ), outOff( n ), outCap( n );
+    std::vector< zc_xz_enc_result > res( n ? n : 1 );
+    string in, out;
+    uint64_t inPos = 0, outPos = 0;
+    for ( size_t i = 0; i < n; ++i )
+    {
+      payOff[ i ] = inPos;
+      paySize[ i ] = payloads[ i ]->size();
+      inPos += paySize[ i ];
+      outOff[ i ] = outPos;
+      outCap[ i ] = zc_xz_capacity( paySize[ i ] );
+      outPos += ( outCap[ i ] + 15 ) / 16 * 16;
+    }
+    in.reserve( inPos ? inPos : 1 );
+    for ( size_t i = 0; i < n; ++i )
+      in += *payloads[ i ];
+    if ( in.empty() )
+      in.resize( 1 );
+    out.resize( outPos ? outPos : 1 );
+    zc_ctx * ctx = pool.acquire();
+    int rc = zc_xz_encode_host( ctx, in.data(), payOff.data(), paySize.data(), n, &out[ 0 ], outOff.data(),
+                                outCap.data(), check, res.data() );
+    string err = rc == ZC_OK ? string() : string( zc_last_error( ctx ) );
+    pool.release( ctx );
+    if ( rc != ZC_OK )
+      throw std::runtime_error( "zc_xz_encode_host: " + err );
+    bodies.resize( n );
+    for ( size_t i = 0; i < n; ++i )
+    {
+      if ( res[ i ].status != ZC_XZ_OK )  // never with zc_xz_capacity's room
+      {
+        char msg[ 96 ];
+        snprintf( msg, sizeof( msg ), "bundle %zu: xz status %d from the encoder", i, (int) res[ i ].status );
+        throw std::runtime_error( msg );
+      }
+      bodies[ i ].assign( out, outOff[ i ], res[ i ].size );
+    }
+  }
+};
+
 /// Adopting a repository stock zbackup wrote: its chunks are known by id only,
 /// and ids alone go through the exact screen at every byte.  This computes the
 /// chunk metadata (zc_chunk_meta) of every chunk of the bundles handed to it

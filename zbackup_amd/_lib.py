@@ -33,7 +33,8 @@ EXPORTS = ["zc_create", "zc_destroy", "zc_seed_index", "zc_get_input_buffer",
            "zc_index_load", "zc_index_load_host", "zc_index_set_counts", "zc_index_set_fetch", "zc_index_set_device",
            "zc_index_set_destroy", "zc_bundle_info_parse", "zc_bundle_info_parse_host", "zc_index_serialize",
            "zc_index_file_size", "zc_index_last_stats",
-           "zc_xz_decode", "zc_xz_decode_host", "zc_xz_last_stats", "zc_device_alloc", "zc_device_free", "zc_upload"]
+           "zc_xz_decode", "zc_xz_decode_host", "zc_xz_last_stats", "zc_device_alloc", "zc_device_free", "zc_upload",
+           "zc_xz_capacity", "zc_xz_encode", "zc_xz_encode_host", "zc_xz_encode_last_stats"]
 (ZC_INDEX_OK, ZC_INDEX_BAD_SIZE, ZC_INDEX_BAD_PADDING, ZC_INDEX_TRUNCATED, ZC_INDEX_BAD_VERSION, ZC_INDEX_BAD_MESSAGE,
  ZC_INDEX_BAD_BUNDLE_ID, ZC_INDEX_BAD_CHUNK_ID, ZC_INDEX_BAD_ADLER) = range(9)
 INDEX_STATUS_NAMES = {0: "ok", 1: "bad file size", 2: "bad padding", 3: "truncated", 4: "unsupported version",
@@ -92,7 +93,12 @@ class ZcXzResult(ctypes.Structure):
                 ("consumed", ctypes.c_uint64)]
 
 
+class ZcXzEncResult(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_int32), ("info", ctypes.c_uint32), ("size", ctypes.c_uint64)]
+
+
 ZC_XZ_OK = 0
+ZC_XZ_E_OUTPUT = 6
 XZ_STATUS_NAMES = {0: "ZC_XZ_OK", 1: "ZC_XZ_E_FORMAT", 2: "ZC_XZ_E_UNSUPPORTED", 3: "ZC_XZ_E_HEADER",
                    4: "ZC_XZ_E_DATA", 5: "ZC_XZ_E_INPUT", 6: "ZC_XZ_E_OUTPUT", 7: "ZC_XZ_E_CHECK",
                    8: "ZC_XZ_E_BUDGET"}
@@ -271,6 +277,10 @@ def load(path=LIB_PATH):
         "zc_xz_decode": (i32, [vp, vp, vp, vp, sz, vp, vp, vp, vp]),
         "zc_xz_decode_host": (i32, [vp, vp, vp, vp, sz, vp, vp, vp, vp]),
         "zc_xz_last_stats": (i32, [vp] + [ctypes.POINTER(ctypes.c_double)] * 3 + [ctypes.POINTER(u64)]),
+        "zc_xz_capacity": (u64, [u64]),
+        "zc_xz_encode": (i32, [vp, vp, vp, vp, sz, vp, vp, vp, u32, vp]),
+        "zc_xz_encode_host": (i32, [vp, vp, vp, vp, sz, vp, vp, vp, u32, vp]),
+        "zc_xz_encode_last_stats": (i32, [vp] + [ctypes.POINTER(ctypes.c_double)] * 4),
         "zc_device_alloc": (i32, [vp, u64, ctypes.POINTER(vp)]),
         "zc_device_free": (i32, [vp, vp]),
         "zc_upload": (i32, [vp, vp, vp, u64]),

@@ -88,6 +88,10 @@ def _bundle_files(prefixes, body_off, body_len, file_off):
     return _Counted(files, len(prefixes)), b"".join(prefixes) or b"\0"
 
 
+XZ_ENC_RESULT_DTYPE = np.dtype([("status", "<i4"), ("info", "<u4"), ("size", "<u8")])
+assert XZ_ENC_RESULT_DTYPE.itemsize == ctypes.sizeof(_lib.ZcXzEncResult)
+
+
 class _Counted:
     """A ctypes array passed by pointer with its element count as len()."""
 
@@ -143,6 +147,62 @@ class BundleCompressor:
                                           len(sizes), out.ctypes.data, out_off.ctypes.data, out_size.ctypes.data)
         _check(self._L, self._ctx, rc, "zc_lzo_compress_host")
         return [out[int(o):int(o) + int(s)].tobytes() for o, s in zip(out_off, out_size)]
+
+    # ---- LZMA bundles (compression.cc:78-97): xz streams instead of framed lzo1x_1 ----
+
+    def xz_capacity(self, n):
+        """Room that always suffices for the xz stream of an n-byte payload (zc_xz_capacity)."""
+        return int(self._L.zc_xz_capacity(int(n)))
+
+    @staticmethod
+    def _xz_judge(res):
+        for k, r in enumerate(res):
+            st = int(r["status"])
+            if st != _lib.ZC_XZ_OK:
+                raise _lib.ZcError(f"bundle {k}: {_lib.XZ_STATUS_NAMES.get(st, st)} (status {st})")
+
+    def compress_xz(self, d_payload, pay_off, pay_size, d_out, out_off, check=4, out_cap=None, strict=True):
+        """The xz stream (zc_xz_encode; check 4 = CRC64, what zbackup writes) of
+        payload i to d_out + out_off[i], room out_cap[i] (None: xz_capacity of
+        its size).  Returns the streams' sizes; raises ZcError naming the first
+        bundle whose room was too small (strict=False: the XZ_ENC_RESULT_DTYPE
+        array instead, the statuses the caller's to read)."""
+        pay_off, pay_size, out_off = _u64(pay_off), _u64(pay_size), _u64(out_off)
+        out_cap = _u64([self.xz_capacity(s) for s in pay_size] if out_cap is None else out_cap)
+        if not len(pay_off) == len(pay_size) == len(out_off) == len(out_cap):
+            raise ValueError("compress_xz: pay_off, pay_size, out_off and out_cap differ in length")
+        res = np.zeros(len(pay_size), dtype=XZ_ENC_RESULT_DTYPE)
+        rc = self._L.zc_xz_encode(self._ctx, d_payload, pay_off.ctypes.data, pay_size.ctypes.data, len(pay_size),
+                                  d_out, out_off.ctypes.data, out_cap.ctypes.data, int(check), res.ctypes.data)
+        _check(self._L, self._ctx, rc, "zc_xz_encode")
+        if not strict:
+            return res
+        self._xz_judge(res)
+        return res["size"].copy()
+
+    def compress_xz_host(self, payloads, check=4):
+        """Host bytes in, xz streams out (zc_xz_encode_host), one call for all."""
+        payloads = [bytes(p) for p in payloads]
+        sizes = np.array([len(p) for p in payloads], dtype=np.uint64)
+        pay_off = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.uint64) if len(sizes) else sizes
+        caps = np.array([(self.xz_capacity(int(s)) + 15) & ~15 for s in sizes], dtype=np.uint64)
+        out_off = np.concatenate([[0], np.cumsum(caps)[:-1]]).astype(np.uint64) if len(caps) else caps
+        src = np.frombuffer(b"".join(payloads) or b"\0", dtype=np.uint8)
+        out = np.zeros(int(caps.sum()) or 1, dtype=np.uint8)
+        res = np.zeros(len(sizes), dtype=XZ_ENC_RESULT_DTYPE)
+        rc = self._L.zc_xz_encode_host(self._ctx, src.ctypes.data, pay_off.ctypes.data, sizes.ctypes.data, len(sizes),
+                                       out.ctypes.data, out_off.ctypes.data, caps.ctypes.data, int(check),
+                                       res.ctypes.data)
+        _check(self._L, self._ctx, rc, "zc_xz_encode_host")
+        self._xz_judge(res)
+        return [out[int(o):int(o) + int(r["size"])].tobytes() for o, r in zip(out_off, res)]
+
+    def xz_last_stats(self):
+        """dict(match_ms, code_ms, check_ms, total_ms) of the last compress_xz."""
+        v = [ctypes.c_double() for _ in range(4)]
+        rc = self._L.zc_xz_encode_last_stats(self._ctx, *[ctypes.byref(x) for x in v])
+        _check(self._L, self._ctx, rc, "zc_xz_encode_last_stats")
+        return dict(zip(("match_ms", "code_ms", "check_ms", "total_ms"), (x.value for x in v)))
 
     def scatter(self, d_src, src_off, sizes, d_dst, dst_off):
         """The inverse of gather: extent i, d_src[src_off[i] ..+ sizes[i]), to

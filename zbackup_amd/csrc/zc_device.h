@@ -648,4 +648,23 @@ int xz_decode(XzScratch* s, bool host, const void* in, const uint64_t* in_off, c
               void* out, const uint64_t* out_off, const uint64_t* out_cap, zc_xz_result* res, hipEvent_t ev_in,
               hipStream_t st, std::string& err);
 
+// zc_xzenc.hip: LZMA bundles, payloads encoded to xz streams (zc_xzenc_core.h).
+// xzenc_validate checks what the host can see (no device, no context);
+// xzenc_encode returns a zc_status with its message in `err`.
+struct XzEncScratch;
+struct XzEncTimes {
+  double match_ms, code_ms, check_ms, total_ms;  // the three kernels over the call's batches, the call's wall clock
+  uint64_t batches;                              // launches of the match and coding kernels
+};
+XzEncScratch* xzenc_scratch_new();
+void xzenc_scratch_free(XzEncScratch* s);
+const XzEncTimes* xzenc_times(const XzEncScratch* s);
+uint64_t xzenc_capacity(uint64_t n);
+int xzenc_validate(const void* pay, const uint64_t* pay_off, const uint64_t* pay_size, size_t n, const void* out,
+                   const uint64_t* out_off, const uint64_t* out_cap, uint32_t check, const zc_xz_enc_result* res,
+                   std::string& err);
+int xzenc_encode(XzEncScratch* s, bool host, const void* pay, const uint64_t* pay_off, const uint64_t* pay_size,
+                 size_t n, void* out, const uint64_t* out_off, const uint64_t* out_cap, uint32_t check,
+                 zc_xz_enc_result* res, hipEvent_t ev_in, hipStream_t st, std::string& err);
+
 }  // namespace zc

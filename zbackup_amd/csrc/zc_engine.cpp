@@ -544,6 +544,7 @@ struct zc_ctx {
   RangeScratch* range = nullptr;  // random-access restore's buffers (zc_range.hip), made on first use
   IndexScratch* index = nullptr;  // index files' buffers (zc_index.hip), made on first use
   XzScratch* xz = nullptr;        // LZMA bundles' buffers (zc_xz.hip), made on first use
+  XzEncScratch* xzenc = nullptr;  // the encoder's tables and candidates (zc_xzenc.hip), made on first use
 
   // scratch
   DevBuf<uint64_t> hm_key, hm_fp, hm_rkey;  // metadata of chunks joining the historic index
@@ -3369,6 +3370,7 @@ int zc_destroy(zc_ctx* c) {
     range_scratch_free(c->range);
     index_scratch_free(c->index);
     xz_scratch_free(c->xz);
+    xzenc_scratch_free(c->xzenc);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     if (prev >= 0) (void)hipSetDevice(prev);
@@ -4805,5 +4807,63 @@ int zc_xz_last_stats(const zc_ctx* c, double* decode_ms, double* check_ms, doubl
   if (check_ms) *check_ms = t.check_ms;
   if (total_ms) *total_ms = t.total_ms;
   if (n_wide) *n_wide = t.n_wide;
+  return ZC_OK;
+}
+
+// ---- LZMA bundles: payloads to xz streams (zc_xzenc.hip) ----
+
+uint64_t zc_xz_capacity(uint64_t payload_size) { return xzenc_capacity(payload_size); }
+
+static int xzenc_entry(zc_ctx* c, const char* what, bool host, const void* pay, const uint64_t* pay_off,
+                       const uint64_t* pay_size, size_t n, void* out, const uint64_t* out_off,
+                       const uint64_t* out_cap, uint32_t check, zc_xz_enc_result* res) {
+  std::string err;
+  if (!c) return ctx_arg_error(c, (std::string(what) + ": null context").c_str());
+  int rc;
+  try {
+    rc = xzenc_validate(pay, pay_off, pay_size, n, out, out_off, out_cap, check, res, err);
+    if (rc != ZC_OK) return ctx_arg_error(c, (std::string(what) + ": " + err).c_str());
+    if (!n) {
+      c->err.clear();
+      return ZC_OK;
+    }
+    DeviceGuard g(c->device);
+    if (!c->xzenc) c->xzenc = xzenc_scratch_new();
+    rc = xzenc_encode(c->xzenc, host, pay, pay_off, pay_size, n, out, out_off, out_cap, check, res,
+                      host ? nullptr : c->ev_in, c->stream, err);
+  } catch (const ZcError& e) {
+    return fail(c, e);
+  } catch (const std::bad_alloc&) {
+    return fail(c, ZcError{ZC_ERR_NOMEM, "host allocation failed"});
+  }
+  if (rc != ZC_OK)
+    c->err = std::string(what) + ": " + err;
+  else
+    c->err.clear();
+  return rc;
+}
+
+int zc_xz_encode(zc_ctx* c, const void* d_payload, const uint64_t* pay_off, const uint64_t* pay_size, size_t n,
+                 void* d_out, const uint64_t* out_off, const uint64_t* out_cap, uint32_t check,
+                 zc_xz_enc_result* res) {
+  ZC_LOCK(c);
+  return xzenc_entry(c, "zc_xz_encode", false, d_payload, pay_off, pay_size, n, d_out, out_off, out_cap, check, res);
+}
+
+int zc_xz_encode_host(zc_ctx* c, const void* payload, const uint64_t* pay_off, const uint64_t* pay_size, size_t n,
+                      void* out, const uint64_t* out_off, const uint64_t* out_cap, uint32_t check,
+                      zc_xz_enc_result* res) {
+  ZC_LOCK(c);
+  return xzenc_entry(c, "zc_xz_encode_host", true, payload, pay_off, pay_size, n, out, out_off, out_cap, check, res);
+}
+
+int zc_xz_encode_last_stats(const zc_ctx* c, double* match_ms, double* code_ms, double* check_ms, double* total_ms) {
+  ZC_LOCK(c);
+  if (!c) return host_arg_error("zc_xz_encode_last_stats: null context");
+  const XzEncTimes t = c->xzenc ? *xzenc_times(c->xzenc) : XzEncTimes{};
+  if (match_ms) *match_ms = t.match_ms;
+  if (code_ms) *code_ms = t.code_ms;
+  if (check_ms) *check_ms = t.check_ms;
+  if (total_ms) *total_ms = t.total_ms;
   return ZC_OK;
 }
