@@ -767,6 +767,87 @@ uint64_t zc_index_file_size(uint64_t body, int keyed);
 int zc_index_last_stats(const zc_ctx* ctx, double* decrypt_ms, double* adler_ms, double* frame_ms,
                         double* records_ms, double* total_ms);
 
+/* ---- Resident chunk index: a backup's chunk ids resolved on the device ----
+ * The reference resolves a restore in three places: ChunkStorage::Reader::get
+ * (chunk_storage.cc:214-260) asks ChunkIndex::findChunk (chunk_index.cc:119-161) which bundle holds
+ * a chunk id; the table it asks was filled by loadIndex / registerNewChunkId
+ * (chunk_index.cc:26-79,163-182); Bundle::Reader (bundle.cc:220-251) then says where the chunk lies
+ * in that bundle's payload.  A zc_chunk_index is that table in HBM for a whole repository -- garbage
+ * collection's exact id table (zc_gc_core.h) with every record's location beside it -- and
+ * zc_restore_resolve turns a parsed BackupInstruction stream into a restore plan against it
+ * (zc_resolve_core.h has the steps).  Callers detect these entry points by their symbols (the ABI
+ * version stays 5).
+ *
+ * Input is zc_gc_input's layout: ids (n_records x 24), sizes, bundle_first (n_bundles + 1).
+ * Owner of an id: the record with the smallest processing position (zc_gc_plan's comment: bundles
+ * in input order, a bundle's records from the last to the first, chunk_index.cc:55) among the
+ * records with that id; so the first bundle in input order that holds the id wins, as in
+ * registerNewChunkId.  A file of a zc_index_set whose status is not ZC_INDEX_OK has contributed
+ * nothing already.
+ * Location: record r of bundle b lies at payload offset = the sum of the sizes of b's records in
+ * front of it, in BundleInfo order (bundle.cc:221-232), 64 bits; b's payload size is the sum over
+ * all of b's records.
+ * Duplicate inside a bundle: a bundle whose records hold one id twice cannot be opened
+ * (exDuplicateChunks, bundle.cc:229-230).  The index flags exactly those bundles, whatever other
+ * bundles hold the same id (a second table keyed by (id, bundle number)); a flagged bundle is an
+ * error only when a resolve uses it.
+ *
+ * zc_chunk_index_create reads a live set's device arrays (no host trip) during the call; the index
+ * keeps its own copy in processing order, so it does not depend on the set afterwards.
+ * zc_chunk_index_create_arrays takes host arrays (what zc_bundle_info_parse gives a caller who
+ * holds only bundle files) and uploads them.  Both run on the context's stream and return with the
+ * index complete; after that it is read-only, holds no stream state, and serves any number of
+ * lookups and resolves from any context of its device.  ZC_ERR_ARG, with a message in zc_last_error
+ * and before any device work: a NULL pointer; 2^32 - 1 or more records or bundles; bundle_first
+ * malformed by zc_gc_plan's rules (not starting at 0, decreasing, not ending at n_records).  Zero
+ * records and zero bundles are legal.  Table sizes follow zc_gc_plan's (a power of two, at least
+ * twice the records); ZC_TEST_RESOLVE_BITS=<b> in the environment shrinks both tables as
+ * ZC_TEST_GC_BITS does: tests only. */
+typedef struct zc_chunk_index zc_chunk_index;
+int zc_chunk_index_create(zc_ctx* ctx, const zc_index_set* set, zc_chunk_index** idx);
+int zc_chunk_index_create_arrays(zc_ctx* ctx, const uint8_t* ids, const uint32_t* sizes, uint64_t n_records,
+                                 const uint64_t* bundle_first, uint64_t n_bundles, zc_chunk_index** idx);
+/* records, bundles, distinct ids, flagged bundles (a NULL pointer skips that count) */
+int zc_chunk_index_counts(const zc_chunk_index* idx, uint64_t* n_records, uint64_t* n_bundles, uint64_t* n_ids,
+                          uint64_t* n_flagged);
+/* per bundle: its payload size and 1 when it holds an id twice (n_bundles each; NULL skips) */
+int zc_chunk_index_bundles(const zc_chunk_index* idx, uint64_t* payload_size, uint8_t* dup);
+/* Batch findChunk: for each of n ids (host, n x 24) the owner's bundle number, payload offset and
+ * size, into host arrays; bundle 0xffffffff (offset and size 0) when the index has no such id. */
+#define ZC_NO_BUNDLE 0xFFFFFFFFu
+int zc_chunk_index_lookup(zc_ctx* ctx, const zc_chunk_index* idx, const uint8_t* ids, size_t n, uint32_t* bundle,
+                          uint64_t* off, uint32_t* size);
+int zc_chunk_index_destroy(zc_chunk_index* idx);
+/* Resolve: ins is the array zc_parse_instructions produced (host; the parse stays on the host, a
+ * serial frame walk), instr_bytes the stream's length.  Entry e of kind CHUNK gets (bundle, off,
+ * size) by lookup; an entry of kind BYTES refers to the instruction stream itself at data_off.
+ * Used bundles are the distinct bundles of CHUNK entries in ascending bundle number; slot k is the
+ * k-th used bundle and slot n_used the instruction stream (zc_range_index_create's convention).
+ * dst[e] is the exclusive running sum of the entry sizes, length the total.  A missing id is not a
+ * failed call: its entry has slot ZC_NO_BUNDLE and size 0, the plan reports n_missing and the
+ * smallest entry that missed (exNoSuchChunk is the caller's to raise, naming ins[first_missing].id).
+ * A used bundle that is flagged duplicate is reported the same way: n_dup_used entries, the first
+ * of them first_dup.  ZC_ERR_ARG before any device work: a NULL pointer; 2^32 - 1 or more entries;
+ * an entry kind other than the two; a BYTES entry that runs past instr_bytes; BYTES sizes whose sum
+ * wraps 2^64.  A length that wraps 2^64 only with the chunk sizes, which the device knows, is
+ * ZC_ERR_ARG after the probe.  Zero entries are legal. */
+typedef struct zc_restore_plan zc_restore_plan;
+int zc_restore_resolve(zc_ctx* ctx, const zc_chunk_index* idx, const zc_instruction* ins, size_t n,
+                       uint64_t instr_bytes, zc_restore_plan** plan);
+/* a NULL pointer skips that count; first_missing / first_dup are 0 when there is none */
+int zc_restore_plan_counts(const zc_restore_plan* plan, uint64_t* n_entries, uint64_t* n_used, uint64_t* length,
+                           uint64_t* n_missing, uint64_t* first_missing, uint64_t* n_dup_used, uint64_t* first_dup);
+/* host arrays (a NULL pointer skips that array): used and used_size (n_used each: the bundle
+ * number and its payload size), and per entry slot, off, size and dst (28 bytes an entry) */
+int zc_restore_plan_fetch(const zc_restore_plan* plan, uint32_t* used, uint64_t* used_size, uint32_t* slot,
+                          uint64_t* off, uint64_t* size, uint64_t* dst);
+int zc_restore_plan_destroy(zc_restore_plan* plan);
+/* The context's last calls: device time of the last index build's kernels and of the last
+ * resolve's or lookup's, and of whichever call came last the table's slots and the longest probe
+ * run an insert or lookup walked. */
+int zc_resolve_last_stats(const zc_ctx* ctx, double* build_ms, double* resolve_ms, uint64_t* table_slots,
+                          uint32_t* max_probe);
+
 /* ---- LZMA bundles: xz streams decoded on the device ----
  * zbackup's default compression method: Bundle::Creator writes a bundle's payload through
  * lzma_easy_encoder(6, LZMA_CHECK_CRC64) (compression.cc:78-97) and Bundle::Reader decodes the body

@@ -1326,4 +1326,192 @@ public:
   uint64_t payloadsEvicted() const { return evictions; }
 };
 
+/// The reader side of ChunkIndex, resident in HBM: loadIndex's table
+/// (chunk_index.cc:26-79,163-182) built from the index files' bytes in one
+/// device pass (zc_index_load_host, zc_chunk_index_create), findChunk
+/// (chunk_index.cc:119-161) for a batch of ids, and the resolve of a whole
+/// backup (ChunkStorage::Reader::get for every chunk_to_emit,
+/// chunk_storage.cc:214-260, with Bundle::Reader's offsets, bundle.cc:220-251)
+/// in one call.  Bundles are numbered in the order loadIndex met them;
+/// bundleId( n ) names the file.  A file that cannot be read contributes
+/// nothing and keeps its status (fileStatus).  The write-side GpuChunkIndex
+/// above is the chunker's seed table and is not touched.  Uses the C ABI only.
+class GpuResidentChunkIndex: NoCopy
+{
+public:
+  enum { NoBundle = 0xFFFFFFFFu };
+
+  struct Found
+  {
+    uint32_t bundle;  // NoBundle: the index has no such chunk
+    uint64_t offset;  // in the bundle's decoded payload
+    uint32_t size;
+  };
+
+  /// a backup resolved: slot k is bundle used[ k ] (ascending), slot used.size() the backup data itself
+  struct Plan
+  {
+    uint64_t length;
+    std::vector< uint32_t > used;
+    std::vector< uint64_t > usedSize;
+    std::vector< uint32_t > slot;
+    std::vector< uint64_t > off, size, dst;
+  };
+
+  struct exNoSuchChunk: std::runtime_error
+  {
+    explicit exNoSuchChunk( string const & what ): std::runtime_error( what ) {}
+  };
+  struct exDuplicateChunks: std::runtime_error
+  {
+    explicit exDuplicateChunks( string const & what ): std::runtime_error( what ) {}
+  };
+
+private:
+  zc_ctx * ctx;
+  zc_chunk_index * index;
+  std::vector< string > bundleIds;
+  std::vector< int > status;
+
+  static string hex( uint8_t const * p, size_t n )
+  {
+    string out;
+    char b[ 3 ];
+    for ( size_t i = 0; i < n; ++i )
+    {
+      snprintf( b, sizeof b, "%02x", p[ i ] );
+      out += b;
+    }
+    return out;
+  }
+
+public:
+  /// indexFiles: the files' bytes, in the order Dir::Listing hands them to loadIndex
+  GpuResidentChunkIndex( std::vector< string > const & indexFiles, EncryptionKey const & encryptionKey,
+                         int device = 0 ): ctx( 0 ), index( 0 )
+  {
+    size_t n = indexFiles.size();
+    std::vector< uint64_t > off( n ), size( n );
+    string in;
+    for ( size_t i = 0; i < n; ++i )
+    {
+      off[ i ] = in.size();
+      size[ i ] = indexFiles[ i ].size();
+      in += indexFiles[ i ];
+      in.resize( ( in.size() + 15 ) / 16 * 16 );  // every file at a 16-byte offset
+    }
+    if ( in.empty() )
+      in.resize( 16 );
+    zcCheck( zc_create( &ctx, 65536, device, 0 ), 0, "zc_create" );
+    zc_index_set * set = 0;
+    uint64_t files = 0, bundles = 0, records = 0;
+    int rc = zc_index_load_host( ctx, encryptionKey.hasKey() ? (uint8_t const *)encryptionKey.getKey() : 0, in.data(),
+                                 off.data(), size.data(), n, &set );
+    string err = rc == ZC_OK ? string() : string( "zc_index_load_host: " ) + zc_last_error( ctx );
+    if ( rc == ZC_OK )
+    {
+      zc_index_set_counts( set, &files, &bundles, &records );
+      std::vector< uint8_t > ids( 24 * bundles + 1 );
+      std::vector< int32_t > st( files + 1 );
+      rc = zc_index_set_fetch( set, 0, 0, 0, ids.data(), 0, st.data() );
+      if ( rc != ZC_OK )
+        err = string( "zc_index_set_fetch: " ) + zc_last_error( 0 );
+      for ( uint64_t b = 0; b < bundles; ++b )
+        bundleIds.push_back( string( (char const *)&ids[ 24 * b ], 24 ) );
+      status.assign( st.begin(), st.begin() + files );
+    }
+    if ( rc == ZC_OK )
+    {
+      rc = zc_chunk_index_create( ctx, set, &index );
+      if ( rc != ZC_OK )
+        err = string( "zc_chunk_index_create: " ) + zc_last_error( ctx );
+    }
+    if ( set )
+      zc_index_set_destroy( set );  // the index keeps its own copy
+    if ( rc != ZC_OK )
+    {
+      zc_destroy( ctx );
+      throw std::runtime_error( err );
+    }
+  }
+
+  ~GpuResidentChunkIndex()
+  {
+    zc_chunk_index_destroy( index );
+    zc_destroy( ctx );
+  }
+
+  size_t bundles() const { return bundleIds.size(); }
+  /// the 24 bytes of bundle n's id (Bundle::Id), which name its file
+  string const & bundleId( size_t n ) const { return bundleIds.at( n ); }
+  /// ZC_INDEX_* per index file given
+  std::vector< int > const & fileStatus() const { return status; }
+
+  void counts( uint64_t & records, uint64_t & ids, uint64_t & flaggedBundles ) const
+  {
+    uint64_t b = 0;
+    if ( zc_chunk_index_counts( index, &records, &b, &ids, &flaggedBundles ) != ZC_OK )
+      throw std::runtime_error( string( "zc_chunk_index_counts: " ) + zc_last_error( 0 ) );
+  }
+
+  /// findChunk for every id (24-byte ChunkId blobs)
+  void findChunks( std::vector< string > const & ids, std::vector< Found > & found )
+  {
+    size_t n = ids.size();
+    std::vector< uint8_t > blobs( 24 * n + 1 );
+    for ( size_t i = 0; i < n; ++i )
+    {
+      if ( ids[ i ].size() != 24 )
+        throw std::runtime_error( "GpuResidentChunkIndex: a chunk id that is not 24 bytes" );
+      memcpy( &blobs[ 24 * i ], ids[ i ].data(), 24 );
+    }
+    std::vector< uint32_t > bundle( n + 1 ), size( n + 1 );
+    std::vector< uint64_t > off( n + 1 );
+    zcCheck( zc_chunk_index_lookup( ctx, index, blobs.data(), n, bundle.data(), off.data(), size.data() ), ctx,
+             "zc_chunk_index_lookup" );
+    found.resize( n );
+    for ( size_t i = 0; i < n; ++i )
+    {
+      Found f = { bundle[ i ], off[ i ], size[ i ] };
+      found[ i ] = f;
+    }
+  }
+
+  /// The whole backup at once.  Throws exNoSuchChunk naming the first chunk no
+  /// bundle holds, exDuplicateChunks naming the first used bundle that holds
+  /// an id twice (Bundle::Reader would refuse to open it).
+  void plan( string const & backupData, Plan & out )
+  {
+    size_t count = 0;
+    zc_parse_instructions( backupData.data(), backupData.size(), 0, 0, &count );
+    std::vector< zc_instruction > ins( count + 1 );
+    if ( zc_parse_instructions( backupData.data(), backupData.size(), ins.data(), ins.size(), &count ) != ZC_OK )
+      throw std::runtime_error( string( "zc_parse_instructions: " ) + zc_last_error( 0 ) );
+    zc_restore_plan * p = 0;
+    zcCheck( zc_restore_resolve( ctx, index, ins.data(), count, backupData.size(), &p ), ctx, "zc_restore_resolve" );
+    uint64_t n = 0, used = 0, missing = 0, firstMissing = 0, dupUsed = 0, firstDup = 0;
+    zc_restore_plan_counts( p, &n, &used, &out.length, &missing, &firstMissing, &dupUsed, &firstDup );
+    out.used.assign( used + 1, 0 );
+    out.usedSize.assign( used + 1, 0 );
+    out.slot.assign( n + 1, 0 );
+    out.off.assign( n + 1, 0 );
+    out.size.assign( n + 1, 0 );
+    out.dst.assign( n + 1, 0 );
+    zc_restore_plan_fetch( p, out.used.data(), out.usedSize.data(), out.slot.data(), out.off.data(), out.size.data(),
+                           out.dst.data() );
+    zc_restore_plan_destroy( p );
+    out.used.resize( used );
+    out.usedSize.resize( used );
+    out.slot.resize( n );
+    out.off.resize( n );
+    out.size.resize( n );
+    out.dst.resize( n );
+    if ( missing )
+      throw exNoSuchChunk( "chunk " + hex( ins[ firstMissing ].id, 24 ) + " is in no bundle of the index" );
+    if ( dupUsed )
+      throw exDuplicateChunks( "bundle " + hex( (uint8_t const *)bundleIds[ out.used[ out.slot[ firstDup ] ] ].data(), 24 ) +
+                               " holds a chunk id twice" );
+  }
+};
+
 #endif

@@ -11,11 +11,12 @@ from .bundle import BundleCompressor, BundleDecompressor, bundle_file_size, pars
 from .restore import IndexedRestorer, RangeIndex, Restorer  # noqa: F401
 from .collect import Collector, GcPlan  # noqa: F401
 from .adopt import Adopter, AdoptReport, read_sidecar, write_sidecar  # noqa: F401
-from .index import BundleInfos, IndexLoader, IndexSet, write_index  # noqa: F401
+from .index import (BundleInfos, ChunkIndex, IndexLoader, IndexSet, ResidentIndexSet, ResolvedStream,  # noqa: F401
+                    write_index)
 
 __all__ = ["BackupCreator", "Sha256", "ZcError", "RECORD_DTYPE", "chunk_id_blob", "serialize_instruction",
            "fill_splitmix64", "load", "META_DTYPE", "anchor_def", "ZC_CHUNK_NEW", "ZC_CHUNK_DUP", "ZC_BYTES",
            "Restorer", "IndexedRestorer", "RangeIndex", "parse_backup_data", "BundleCompressor", "BundleDecompressor",
            "bundle_file_size",
            "Collector", "GcPlan", "Adopter", "AdoptReport", "write_sidecar", "read_sidecar",
-           "IndexLoader", "IndexSet", "BundleInfos", "write_index"]
+           "IndexLoader", "IndexSet", "BundleInfos", "write_index", "ChunkIndex", "ResidentIndexSet", "ResolvedStream"]

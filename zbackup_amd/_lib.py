@@ -34,7 +34,10 @@ EXPORTS = ["zc_create", "zc_destroy", "zc_seed_index", "zc_get_input_buffer",
            "zc_index_set_destroy", "zc_bundle_info_parse", "zc_bundle_info_parse_host", "zc_index_serialize",
            "zc_index_file_size", "zc_index_last_stats",
            "zc_xz_decode", "zc_xz_decode_host", "zc_xz_last_stats", "zc_device_alloc", "zc_device_free", "zc_upload",
-           "zc_xz_capacity", "zc_xz_encode", "zc_xz_encode_host", "zc_xz_encode_last_stats"]
+           "zc_xz_capacity", "zc_xz_encode", "zc_xz_encode_host", "zc_xz_encode_last_stats",
+           "zc_chunk_index_create", "zc_chunk_index_create_arrays", "zc_chunk_index_counts", "zc_chunk_index_bundles",
+           "zc_chunk_index_lookup", "zc_chunk_index_destroy", "zc_restore_resolve", "zc_restore_plan_counts",
+           "zc_restore_plan_fetch", "zc_restore_plan_destroy", "zc_resolve_last_stats"]
 (ZC_INDEX_OK, ZC_INDEX_BAD_SIZE, ZC_INDEX_BAD_PADDING, ZC_INDEX_TRUNCATED, ZC_INDEX_BAD_VERSION, ZC_INDEX_BAD_MESSAGE,
  ZC_INDEX_BAD_BUNDLE_ID, ZC_INDEX_BAD_CHUNK_ID, ZC_INDEX_BAD_ADLER) = range(9)
 INDEX_STATUS_NAMES = {0: "ok", 1: "bad file size", 2: "bad padding", 3: "truncated", 4: "unsupported version",
@@ -54,6 +57,7 @@ BUNDLE_STATUS_NAMES = {0: "ok", 1: "bad file size", 2: "truncated", 3: "Adler-32
 ZC_LZO_E_FRAME, ZC_LZO_E_SIZE = -100, -101
 ZC_INSTR_CHUNK, ZC_INSTR_BYTES = 0, 1
 ZC_META_NO_ANCHOR = 0xFFFFFFFF
+ZC_NO_BUNDLE = 0xFFFFFFFF
 
 
 class ZcRecord(ctypes.Structure):
@@ -281,6 +285,22 @@ def load(path=LIB_PATH):
         "zc_xz_encode": (i32, [vp, vp, vp, vp, sz, vp, vp, vp, u32, vp]),
         "zc_xz_encode_host": (i32, [vp, vp, vp, vp, sz, vp, vp, vp, u32, vp]),
         "zc_xz_encode_last_stats": (i32, [vp] + [ctypes.POINTER(ctypes.c_double)] * 4),
+        # resident chunk index: (ctx, set, &idx); (ctx, ids, sizes, n_records, bundle_first, n_bundles, &idx)
+        "zc_chunk_index_create": (i32, [vp, vp, ctypes.POINTER(vp)]),
+        "zc_chunk_index_create_arrays": (i32, [vp, vp, vp, u64, vp, u64, ctypes.POINTER(vp)]),
+        "zc_chunk_index_counts": (i32, [vp] + [ctypes.POINTER(u64)] * 4),
+        "zc_chunk_index_bundles": (i32, [vp, vp, vp]),
+        # (ctx, idx, ids, n, bundle, off, size)
+        "zc_chunk_index_lookup": (i32, [vp, vp, vp, sz, vp, vp, vp]),
+        "zc_chunk_index_destroy": (i32, [vp]),
+        # (ctx, idx, ins, n, instr_bytes, &plan)
+        "zc_restore_resolve": (i32, [vp, vp, vp, sz, u64, ctypes.POINTER(vp)]),
+        "zc_restore_plan_counts": (i32, [vp] + [ctypes.POINTER(u64)] * 7),
+        # (plan, used, used_size, slot, off, size, dst)
+        "zc_restore_plan_fetch": (i32, [vp, vp, vp, vp, vp, vp, vp]),
+        "zc_restore_plan_destroy": (i32, [vp]),
+        "zc_resolve_last_stats": (i32, [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
+                                        ctypes.POINTER(u64), ctypes.POINTER(u32)]),
         "zc_device_alloc": (i32, [vp, u64, ctypes.POINTER(vp)]),
         "zc_device_free": (i32, [vp, vp]),
         "zc_upload": (i32, [vp, vp, vp, u64]),

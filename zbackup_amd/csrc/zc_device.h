@@ -625,9 +625,51 @@ int index_set_fetch(const zc_index_set* set, uint8_t* ids, uint32_t* sizes, uint
                     uint8_t* bundle_ids, uint64_t* index_first, int32_t* status, std::string& err);
 void index_set_device(const zc_index_set* set, const void** d_ids, const void** d_sizes);
 void index_set_destroy(zc_index_set* set);
+// the set's device and its device arrays (bundle_first too), for zc_resolve.hip
+void index_set_arrays(const zc_index_set* set, int* device, const void** d_ids, const void** d_sizes,
+                      const uint64_t** d_bundle_first);
 int index_serialize(const uint8_t* ids, const uint32_t* sizes, const uint64_t* bundle_first,
                     const uint8_t* bundle_ids, uint64_t n_bundles, uint8_t* out, uint64_t cap, uint64_t* n_out,
                     std::string& err);
+
+// zc_resolve.hip: the resident chunk index and the resolve of a backup against
+// it (zc_resolve_core.h).  chunk_index_validate / resolve_validate check what
+// the host can see (no device, no context); each call returns a zc_status with
+// its message in `err`.
+struct ResolveScratch;
+struct ResolveTimes {
+  double build_ms, resolve_ms;  // the last build's kernels; the last resolve's or lookup's
+  uint64_t table_slots;         // of the index the last call built or read
+  uint32_t max_probe;           // the longest probe run of the last call
+};
+ResolveScratch* resolve_scratch_new();
+void resolve_scratch_free(ResolveScratch* s);
+const ResolveTimes* resolve_times(const ResolveScratch* s);
+// host: ids, sizes and bundle_first are host arrays (bundle_first is checked,
+// all three uploaded); else they are a zc_index_set's device arrays
+int chunk_index_validate(bool host, const void* ids, const void* sizes, uint64_t n_records,
+                         const uint64_t* bundle_first, uint64_t n_bundles, zc_chunk_index* const* out,
+                         std::string& err);
+int chunk_index_build(ResolveScratch* s, int device, bool host, const void* ids, const void* sizes,
+                      uint64_t n_records, const uint64_t* bundle_first, uint64_t n_bundles, zc_chunk_index** out,
+                      hipStream_t st, std::string& err);
+void chunk_index_counts(const zc_chunk_index* ix, uint64_t* n_records, uint64_t* n_bundles, uint64_t* n_ids,
+                        uint64_t* n_flagged);
+int chunk_index_device(const zc_chunk_index* ix);
+int chunk_index_bundles(const zc_chunk_index* ix, uint64_t* payload_size, uint8_t* dup, std::string& err);
+void chunk_index_destroy(zc_chunk_index* ix);
+int chunk_index_lookup(ResolveScratch* s, const zc_chunk_index* ix, const uint8_t* ids, uint64_t n, uint32_t* bundle,
+                       uint64_t* off, uint32_t* size, hipStream_t st, std::string& err);
+// *bytes_total: the sum of the BYTES entries' sizes, which restore_resolve takes
+int resolve_validate(const zc_instruction* ins, uint64_t n, uint64_t instr_bytes, zc_restore_plan* const* out,
+                     uint64_t* bytes_total, std::string& err);
+int restore_resolve(ResolveScratch* s, const zc_chunk_index* ix, const zc_instruction* ins, uint64_t n,
+                    uint64_t bytes_total, zc_restore_plan** out, hipStream_t st, std::string& err);
+void restore_plan_counts(const zc_restore_plan* pl, uint64_t* n_entries, uint64_t* n_used, uint64_t* length,
+                         uint64_t* n_missing, uint64_t* first_missing, uint64_t* n_dup_used, uint64_t* first_dup);
+void restore_plan_fetch(const zc_restore_plan* pl, uint32_t* used, uint64_t* used_size, uint32_t* slot, uint64_t* off,
+                        uint64_t* size, uint64_t* dst);
+void restore_plan_destroy(zc_restore_plan* pl);
 
 // zc_xz.hip: LZMA bundles, xz streams decoded to their payloads (zc_xz_core.h).
 // xz_validate checks what the host can see (no device, no context); xz_decode

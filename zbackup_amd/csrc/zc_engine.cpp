@@ -543,6 +543,7 @@ struct zc_ctx {
   MetaScratch* meta = nullptr;  // adoption's buffers (zc_meta.hip), made on first use
   RangeScratch* range = nullptr;  // random-access restore's buffers (zc_range.hip), made on first use
   IndexScratch* index = nullptr;  // index files' buffers (zc_index.hip), made on first use
+  ResolveScratch* rs = nullptr;   // the chunk index's build and resolve buffers (zc_resolve.hip), made on first use
   XzScratch* xz = nullptr;        // LZMA bundles' buffers (zc_xz.hip), made on first use
   XzEncScratch* xzenc = nullptr;  // the encoder's tables and candidates (zc_xzenc.hip), made on first use
 
@@ -3369,6 +3370,7 @@ int zc_destroy(zc_ctx* c) {
     meta_scratch_free(c->meta);
     range_scratch_free(c->range);
     index_scratch_free(c->index);
+    resolve_scratch_free(c->rs);
     xz_scratch_free(c->xz);
     xzenc_scratch_free(c->xzenc);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -4705,6 +4707,164 @@ int zc_index_last_stats(const zc_ctx* c, double* decrypt_ms, double* adler_ms, d
   if (frame_ms) *frame_ms = t.frame_ms;
   if (records_ms) *records_ms = t.records_ms;
   if (total_ms) *total_ms = t.total_ms;
+  return ZC_OK;
+}
+
+// ---- the resident chunk index and the resolve against it (zc_resolve.hip) ----
+
+// the common frame of the device calls below, as index_entry
+template <class F>
+static int resolve_entry(zc_ctx* c, const char* what, int checked, std::string& err, F&& f) {
+  if (checked != ZC_OK) return ctx_arg_error(c, (std::string(what) + ": " + err).c_str());
+  if (!c) return ctx_arg_error(c, (std::string(what) + ": null context").c_str());
+  int rc;
+  try {
+    DeviceGuard g(c->device);
+    if (!c->rs) c->rs = resolve_scratch_new();
+    rc = f(err);
+  } catch (const ZcError& e) {
+    return fail(c, e);
+  } catch (const std::bad_alloc&) {
+    return fail(c, ZcError{ZC_ERR_NOMEM, "host allocation failed"});
+  }
+  if (rc != ZC_OK)
+    c->err = std::string(what) + ": " + err;
+  else
+    c->err.clear();
+  return rc;
+}
+
+int zc_chunk_index_create(zc_ctx* c, const zc_index_set* set, zc_chunk_index** idx) {
+  ZC_LOCK(c);
+  std::string err;
+  int checked = ZC_OK, device = 0;
+  uint64_t B = 0, N = 0;
+  const void *d_ids = nullptr, *d_sizes = nullptr;
+  const uint64_t* d_bf = nullptr;
+  if (!set) {
+    err = "null set";
+    checked = ZC_ERR_ARG;
+  } else {
+    index_set_counts(set, nullptr, &B, &N);
+    index_set_arrays(set, &device, &d_ids, &d_sizes, &d_bf);
+    checked = chunk_index_validate(false, d_ids, d_sizes, N, d_bf, B, idx, err);
+    if (checked == ZC_OK && c && device != c->device) {
+      err = "the set lives on another device than the context";
+      checked = ZC_ERR_ARG;
+    }
+  }
+  return resolve_entry(c, "zc_chunk_index_create", checked, err, [&](std::string& e) {
+    return chunk_index_build(c->rs, c->device, false, d_ids, d_sizes, N, d_bf, B, idx, c->stream, e);
+  });
+}
+
+int zc_chunk_index_create_arrays(zc_ctx* c, const uint8_t* ids, const uint32_t* sizes, uint64_t n_records,
+                                 const uint64_t* bundle_first, uint64_t n_bundles, zc_chunk_index** idx) {
+  ZC_LOCK(c);
+  std::string err;
+  const int checked = chunk_index_validate(true, ids, sizes, n_records, bundle_first, n_bundles, idx, err);
+  return resolve_entry(c, "zc_chunk_index_create_arrays", checked, err, [&](std::string& e) {
+    return chunk_index_build(c->rs, c->device, true, ids, sizes, n_records, bundle_first, n_bundles, idx, c->stream,
+                             e);
+  });
+}
+
+// the index's and the plan's own calls take no context: their message is the thread's
+
+int zc_chunk_index_counts(const zc_chunk_index* idx, uint64_t* n_records, uint64_t* n_bundles, uint64_t* n_ids,
+                          uint64_t* n_flagged) {
+  if (!idx) return host_arg_error("zc_chunk_index_counts: null index");
+  chunk_index_counts(idx, n_records, n_bundles, n_ids, n_flagged);
+  return ZC_OK;
+}
+
+int zc_chunk_index_bundles(const zc_chunk_index* idx, uint64_t* payload_size, uint8_t* dup) {
+  if (!idx) return host_arg_error("zc_chunk_index_bundles: null index");
+  std::string err;
+  const int rc = chunk_index_bundles(idx, payload_size, dup, err);
+  g_host_err = rc != ZC_OK ? "zc_chunk_index_bundles: " + err : std::string();
+  return rc;
+}
+
+int zc_chunk_index_destroy(zc_chunk_index* idx) {
+  if (!idx) return host_arg_error("zc_chunk_index_destroy: null index");
+  chunk_index_destroy(idx);
+  return ZC_OK;
+}
+
+int zc_chunk_index_lookup(zc_ctx* c, const zc_chunk_index* idx, const uint8_t* ids, size_t n, uint32_t* bundle,
+                          uint64_t* off, uint32_t* size) {
+  ZC_LOCK(c);
+  std::string err;
+  int checked = ZC_OK;
+  if (!idx) {
+    err = "null index";
+    checked = ZC_ERR_ARG;
+  } else if (n && (!ids || !bundle || !off || !size)) {
+    err = "null pointer";
+    checked = ZC_ERR_ARG;
+  } else if (n >= 0xffffffffull) {
+    err = "2^32 - 1 ids or more";
+    checked = ZC_ERR_ARG;
+  } else if (c && chunk_index_device(idx) != c->device) {
+    err = "the index lives on another device than the context";
+    checked = ZC_ERR_ARG;
+  }
+  return resolve_entry(c, "zc_chunk_index_lookup", checked, err, [&](std::string& e) {
+    return chunk_index_lookup(c->rs, idx, ids, n, bundle, off, size, c->stream, e);
+  });
+}
+
+int zc_restore_resolve(zc_ctx* c, const zc_chunk_index* idx, const zc_instruction* ins, size_t n,
+                       uint64_t instr_bytes, zc_restore_plan** plan) {
+  ZC_LOCK(c);
+  std::string err;
+  int checked = ZC_OK;
+  uint64_t bytes_total = 0;
+  if (!idx) {
+    err = "null index";
+    checked = ZC_ERR_ARG;
+  } else {
+    checked = resolve_validate(ins, n, instr_bytes, plan, &bytes_total, err);
+    if (checked == ZC_OK && c && chunk_index_device(idx) != c->device) {
+      err = "the index lives on another device than the context";
+      checked = ZC_ERR_ARG;
+    }
+  }
+  return resolve_entry(c, "zc_restore_resolve", checked, err, [&](std::string& e) {
+    return restore_resolve(c->rs, idx, ins, n, bytes_total, plan, c->stream, e);
+  });
+}
+
+int zc_restore_plan_counts(const zc_restore_plan* plan, uint64_t* n_entries, uint64_t* n_used, uint64_t* length,
+                           uint64_t* n_missing, uint64_t* first_missing, uint64_t* n_dup_used, uint64_t* first_dup) {
+  if (!plan) return host_arg_error("zc_restore_plan_counts: null plan");
+  restore_plan_counts(plan, n_entries, n_used, length, n_missing, first_missing, n_dup_used, first_dup);
+  return ZC_OK;
+}
+
+int zc_restore_plan_fetch(const zc_restore_plan* plan, uint32_t* used, uint64_t* used_size, uint32_t* slot,
+                          uint64_t* off, uint64_t* size, uint64_t* dst) {
+  if (!plan) return host_arg_error("zc_restore_plan_fetch: null plan");
+  restore_plan_fetch(plan, used, used_size, slot, off, size, dst);
+  return ZC_OK;
+}
+
+int zc_restore_plan_destroy(zc_restore_plan* plan) {
+  if (!plan) return host_arg_error("zc_restore_plan_destroy: null plan");
+  restore_plan_destroy(plan);
+  return ZC_OK;
+}
+
+int zc_resolve_last_stats(const zc_ctx* c, double* build_ms, double* resolve_ms, uint64_t* table_slots,
+                          uint32_t* max_probe) {
+  ZC_LOCK(c);
+  if (!c) return host_arg_error("zc_resolve_last_stats: null context");
+  const ResolveTimes t = c->rs ? *resolve_times(c->rs) : ResolveTimes{};
+  if (build_ms) *build_ms = t.build_ms;
+  if (resolve_ms) *resolve_ms = t.resolve_ms;
+  if (table_slots) *table_slots = t.table_slots;
+  if (max_probe) *max_probe = t.max_probe;
   return ZC_OK;
 }
 

@@ -1070,6 +1070,14 @@ void index_set_device(const zc_index_set* set, const void** d_ids, const void** 
   if (d_sizes) *d_sizes = set->n_records ? set->sizes.p : nullptr;
 }
 
+void index_set_arrays(const zc_index_set* set, int* device, const void** d_ids, const void** d_sizes,
+                      const uint64_t** d_bundle_first) {
+  *device = set->device;
+  *d_ids = set->ids.p;
+  *d_sizes = set->sizes.p;
+  *d_bundle_first = set->bundle_first.p;
+}
+
 void index_set_destroy(zc_index_set* set) {
   SetDevice g(set->device);
   delete set;

@@ -102,25 +102,55 @@ class IndexLoader:
             src[int(o):int(o) + len(f)] = np.frombuffer(f, dtype=np.uint8)
         return src, off, size
 
-    def _fetch(self, handle):
+    def _fetch_arrays(self, handle):
         nf, nb, nr = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        _host_check(self._L, self._L.zc_index_set_counts(handle, ctypes.byref(nf), ctypes.byref(nb),
+                                                         ctypes.byref(nr)), "zc_index_set_counts")
+        s = IndexSet()
+        s.ids = np.zeros((nr.value, 24), dtype=np.uint8)
+        s.sizes = np.zeros(nr.value, dtype=np.uint32)
+        s.bundle_first = np.zeros(nb.value + 1, dtype=np.uint64)
+        s.bundle_ids = np.zeros((nb.value, 24), dtype=np.uint8)
+        s.index_first = np.zeros(nf.value + 1, dtype=np.uint64)
+        s.status = np.zeros(nf.value, dtype=np.int32)
+        rc = self._L.zc_index_set_fetch(handle, s.ids.ctypes.data, s.sizes.ctypes.data,
+                                        s.bundle_first.ctypes.data, s.bundle_ids.ctypes.data,
+                                        s.index_first.ctypes.data, s.status.ctypes.data)
+        _host_check(self._L, rc, "zc_index_set_fetch")
+        return s
+
+    def _fetch(self, handle):
         try:
-            _host_check(self._L, self._L.zc_index_set_counts(handle, ctypes.byref(nf), ctypes.byref(nb),
-                                                             ctypes.byref(nr)), "zc_index_set_counts")
-            s = IndexSet()
-            s.ids = np.zeros((nr.value, 24), dtype=np.uint8)
-            s.sizes = np.zeros(nr.value, dtype=np.uint32)
-            s.bundle_first = np.zeros(nb.value + 1, dtype=np.uint64)
-            s.bundle_ids = np.zeros((nb.value, 24), dtype=np.uint8)
-            s.index_first = np.zeros(nf.value + 1, dtype=np.uint64)
-            s.status = np.zeros(nf.value, dtype=np.int32)
-            rc = self._L.zc_index_set_fetch(handle, s.ids.ctypes.data, s.sizes.ctypes.data,
-                                            s.bundle_first.ctypes.data, s.bundle_ids.ctypes.data,
-                                            s.index_first.ctypes.data, s.status.ctypes.data)
-            _host_check(self._L, rc, "zc_index_set_fetch")
-            return s
+            return self._fetch_arrays(handle)
         finally:
             self._L.zc_index_set_destroy(handle)
+
+    def load_resident(self, files):
+        """load() without the host trip: returns a ResidentIndexSet, which
+        keeps the zc_index_set -- the records in HBM -- alive until it is
+        closed.  ChunkIndex.from_index_set builds on it."""
+        src, off, size = self._pack(files)
+        handle = ctypes.c_void_p()
+        t = time.perf_counter()
+        rc = self._L.zc_index_load_host(self._ctx, self._key, src.ctypes.data, off.ctypes.data, size.ctypes.data,
+                                        len(size), ctypes.byref(handle))
+        self._call_ms = (time.perf_counter() - t) * 1e3
+        _check(self._L, self._ctx, rc, "zc_index_load_host")
+        return ResidentIndexSet(self, handle)
+
+    def load_resident_device(self, d_files, file_off, file_size):
+        """load_device() without the host trip (see load_resident)."""
+        off = np.ascontiguousarray(file_off, dtype=np.uint64)
+        size = np.ascontiguousarray(file_size, dtype=np.uint64)
+        if len(off) != len(size):
+            raise _lib.ZcError("zc_index_load: file_off and file_size differ in length")
+        handle = ctypes.c_void_p()
+        t = time.perf_counter()
+        rc = self._L.zc_index_load(self._ctx, self._key, ctypes.c_void_p(d_files), off.ctypes.data, size.ctypes.data,
+                                   len(size), ctypes.byref(handle))
+        self._call_ms = (time.perf_counter() - t) * 1e3
+        _check(self._L, self._ctx, rc, "zc_index_load")
+        return ResidentIndexSet(self, handle)
 
     def load(self, files):
         """files: the index files' bytes, in the order their records are to
@@ -203,6 +233,193 @@ class IndexLoader:
 
     def close(self):
         self._comp.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class ResidentIndexSet:
+    """A live zc_index_set: the records of a set of index files, kept in HBM
+    (IndexLoader.load_resident).  `n_files`, `n_bundles`, `n_records`;
+    `fetch()` copies the arrays out as an IndexSet; `close()` frees them."""
+
+    def __init__(self, loader, handle):
+        self._loader, self._L, self._handle = loader, loader._L, handle
+        nf, nb, nr = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        _host_check(self._L, self._L.zc_index_set_counts(handle, ctypes.byref(nf), ctypes.byref(nb),
+                                                         ctypes.byref(nr)), "zc_index_set_counts")
+        self.n_files, self.n_bundles, self.n_records = nf.value, nb.value, nr.value
+
+    def fetch(self):
+        if self._handle is None:
+            raise _lib.ZcError("ResidentIndexSet: closed")
+        return self._loader._fetch_arrays(self._handle)
+
+    def close(self):
+        if self._handle is not None:
+            self._L.zc_index_set_destroy(self._handle)
+            self._handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class ResolvedStream:
+    """zc_restore_resolve's plan on the host: the counts (`n_entries`,
+    `n_used`, `length`, `n_missing`, `first_missing`, `n_dup_used`,
+    `first_dup`), `used` / `used_size` per used bundle (ascending bundle
+    number), and per entry `slot`, `off`, `size`, `dst`.  Slot k is bundle
+    used[k], slot n_used the instruction stream, ZC_NO_BUNDLE a missing id."""
+    COUNTS = ("n_entries", "n_used", "length", "n_missing", "first_missing", "n_dup_used", "first_dup")
+    __slots__ = COUNTS + ("used", "used_size", "slot", "off", "size", "dst")
+
+
+class ChunkIndex:
+    """A zc_chunk_index: ChunkIndex::findChunk for a whole repository in HBM.
+    The owner of an id is its first registration in loadIndex order; a bundle
+    that holds an id twice is flagged.  Made from a live set
+    (`from_index_set`), from arrays in zc_gc_input's layout (`from_arrays`) or
+    from bundles' record lists (`from_bundles`: a BundleInfos, or
+    [[(chunk id, size), ...], ...]); on a context of its own, or on another
+    object's (`ctx=comp._ctx`)."""
+
+    def __init__(self, device=0, ctx=None):
+        self._comp = BundleCompressor(device=device, ctx=ctx)
+        self._L, self._ctx = self._comp._L, self._comp._ctx
+        self._idx = None
+
+    @classmethod
+    def from_index_set(cls, resident, device=0, ctx=None):
+        if not isinstance(resident, ResidentIndexSet) or resident._handle is None:
+            raise _lib.ZcError("ChunkIndex.from_index_set takes a live ResidentIndexSet (IndexLoader.load_resident)")
+        self = cls(device=device, ctx=ctx if ctx is not None else resident._loader._ctx)
+        try:
+            idx = ctypes.c_void_p()
+            rc = self._L.zc_chunk_index_create(self._ctx, resident._handle, ctypes.byref(idx))
+            _check(self._L, self._ctx, rc, "zc_chunk_index_create")
+            self._idx = idx
+        except Exception:
+            self.close()
+            raise
+        return self
+
+    @classmethod
+    def from_arrays(cls, ids, sizes, bundle_first, device=0, ctx=None):
+        ids = np.ascontiguousarray(ids, dtype=np.uint8).reshape(-1, 24)
+        sizes = np.ascontiguousarray(sizes, dtype=np.uint32)
+        bundle_first = np.ascontiguousarray(bundle_first, dtype=np.uint64)
+        if len(ids) != len(sizes) or len(bundle_first) < 1:
+            raise _lib.ZcError("ChunkIndex.from_arrays: ids and sizes differ in length, or bundle_first is empty")
+        self = cls(device=device, ctx=ctx)
+        try:
+            idx = ctypes.c_void_p()
+            rc = self._L.zc_chunk_index_create_arrays(self._ctx, ids.ctypes.data if len(ids) else None,
+                                                      sizes.ctypes.data if len(ids) else None, len(ids),
+                                                      bundle_first.ctypes.data, len(bundle_first) - 1,
+                                                      ctypes.byref(idx))
+            _check(self._L, self._ctx, rc, "zc_chunk_index_create_arrays")
+            self._idx = idx
+        except Exception:
+            self.close()
+            raise
+        return self
+
+    @classmethod
+    def from_bundles(cls, bundles, device=0, ctx=None):
+        if isinstance(bundles, BundleInfos):
+            return cls.from_arrays(bundles.ids, bundles.sizes, bundles.bundle_first, device=device, ctx=ctx)
+        recs = [r for rs in bundles for r in rs]
+        ids = _blobs([c for c, _ in recs], "a chunk id")
+        sizes = np.array([int(s) for _, s in recs], dtype=np.uint32)
+        first = np.concatenate([[0], np.cumsum([len(rs) for rs in bundles])]).astype(np.uint64)
+        return cls.from_arrays(ids, sizes, first, device=device, ctx=ctx)
+
+    def _live(self):
+        if self._idx is None:
+            raise _lib.ZcError("ChunkIndex: closed")
+        return self._idx
+
+    def counts(self):
+        """{records, bundles, ids (distinct), flagged (bundles holding an id twice)}"""
+        c = [ctypes.c_uint64() for _ in range(4)]
+        _host_check(self._L, self._L.zc_chunk_index_counts(self._live(), *[ctypes.byref(x) for x in c]),
+                    "zc_chunk_index_counts")
+        return dict(zip(("records", "bundles", "ids", "flagged"), (x.value for x in c)))
+
+    def bundles(self):
+        """(payload size of every bundle, uint64; whether it holds an id twice, bool)"""
+        nb = self.counts()["bundles"]
+        size, dup = np.zeros(nb, dtype=np.uint64), np.zeros(nb, dtype=np.uint8)
+        rc = self._L.zc_chunk_index_bundles(self._live(), size.ctypes.data if nb else None,
+                                            dup.ctypes.data if nb else None)
+        _host_check(self._L, rc, "zc_chunk_index_bundles")
+        return size, dup.astype(bool)
+
+    def lookup(self, ids):
+        """Batch findChunk: (bundle, off, size) arrays for ids (n x 24 array or
+        a list of 24-byte blobs); bundle ZC_NO_BUNDLE where the index has no such id."""
+        if not isinstance(ids, np.ndarray):
+            ids = _blobs(ids, "a chunk id")
+        ids = np.ascontiguousarray(ids, dtype=np.uint8).reshape(-1, 24)
+        n = len(ids)
+        bundle, off = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint64)
+        size = np.zeros(n, dtype=np.uint32)
+        rc = self._L.zc_chunk_index_lookup(self._ctx, self._live(), ids.ctypes.data if n else None, n,
+                                           bundle.ctypes.data if n else None, off.ctypes.data if n else None,
+                                           size.ctypes.data if n else None)
+        _check(self._L, self._ctx, rc, "zc_chunk_index_lookup")
+        return bundle, off, size
+
+    def resolve(self, ins, instr_bytes):
+        """zc_restore_resolve over parse_backup_data's array; returns a
+        ResolvedStream.  A missing id or a flagged used bundle is reported in
+        its counts, not raised (Restorer.plan_index raises)."""
+        from .bundle import INSTRUCTION_DTYPE
+        ins = np.ascontiguousarray(ins, dtype=INSTRUCTION_DTYPE)
+        n = len(ins)
+        plan = ctypes.c_void_p()
+        rc = self._L.zc_restore_resolve(self._ctx, self._live(), ins.ctypes.data if n else None, n,
+                                        int(instr_bytes), ctypes.byref(plan))
+        _check(self._L, self._ctx, rc, "zc_restore_resolve")
+        try:
+            c = [ctypes.c_uint64() for _ in ResolvedStream.COUNTS]
+            _host_check(self._L, self._L.zc_restore_plan_counts(plan, *[ctypes.byref(x) for x in c]),
+                        "zc_restore_plan_counts")
+            r = ResolvedStream()
+            for name, x in zip(ResolvedStream.COUNTS, c):
+                setattr(r, name, x.value)
+            r.used, r.used_size = np.zeros(r.n_used, dtype=np.uint32), np.zeros(r.n_used, dtype=np.uint64)
+            r.slot = np.zeros(n, dtype=np.uint32)
+            r.off, r.size, r.dst = (np.zeros(n, dtype=np.uint64) for _ in range(3))
+            rc = self._L.zc_restore_plan_fetch(plan, *[a.ctypes.data if len(a) else None
+                                                       for a in (r.used, r.used_size, r.slot, r.off, r.size, r.dst)])
+            _host_check(self._L, rc, "zc_restore_plan_fetch")
+            return r
+        finally:
+            self._L.zc_restore_plan_destroy(plan)
+
+    def last_stats(self):
+        """{build_ms, resolve_ms, table_slots, max_probe} of the context's
+        last build and last resolve or lookup (zc_resolve_last_stats)."""
+        b, r, slots, probe = ctypes.c_double(), ctypes.c_double(), ctypes.c_uint64(), ctypes.c_uint32()
+        rc = self._L.zc_resolve_last_stats(self._ctx, ctypes.byref(b), ctypes.byref(r), ctypes.byref(slots),
+                                           ctypes.byref(probe))
+        _check(self._L, self._ctx, rc, "zc_resolve_last_stats")
+        return {"build_ms": b.value, "resolve_ms": r.value, "table_slots": slots.value, "max_probe": probe.value}
+
+    def close(self):
+        if self._idx is not None:
+            self._L.zc_chunk_index_destroy(self._idx)
+            self._idx = None
+        if self._comp is not None:
+            self._comp.close()
+            self._comp = None
 
     def __enter__(self):
         return self

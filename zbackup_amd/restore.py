@@ -60,7 +60,7 @@ class RestorePlan:
     of `work_size` bytes, the instruction stream `data` at `instr_off`; the
     scatter list is src_off / sizes / dst_off."""
     __slots__ = ("data", "length", "used", "pay_off", "pay_size", "instr_off", "work_size", "src_off", "sizes",
-                 "dst_off")
+                 "dst_off", "slot", "off")  # slot / off: plan_index's fetched arrays (RangeIndex's form)
 
     def host_image(self, payloads):
         """The scratch buffer's contents as one host array, for one upload:
@@ -133,6 +133,41 @@ class Restorer:
         p.dst_off = (np.concatenate([[0], np.cumsum(p.sizes)[:-1]]).astype(np.uint64) if len(entries)
                      else np.zeros(0, dtype=np.uint64))
         p.length = int(p.sizes.sum())
+        return p
+
+    @staticmethod
+    def plan_index(backup_data, chunk_index):
+        """plan() against a resident ChunkIndex (zc_restore_resolve): the
+        caller names no bundles, the index says which ones the stream needs.
+        The fields mean what plan()'s mean, with `used` -- bundle numbers in
+        the index's input order -- ascending, not in first-use order.  Raises
+        ZcError naming the id when the index has no such chunk, and naming the
+        bundle when a used bundle holds an id twice (exDuplicateChunks)."""
+        backup_data = bytes(backup_data)
+        ins = parse_backup_data(backup_data)
+        r = chunk_index.resolve(ins, len(backup_data))
+        if r.n_missing:
+            blob = ins[r.first_missing]["id"].tobytes()
+            raise _lib.ZcError(f"restore: chunk id {blob.hex()} is in none of the "
+                               f"{chunk_index.counts()['bundles']} bundles ({r.n_missing} entries miss)")
+        if r.n_dup_used:
+            b = int(r.used[r.slot[r.first_dup]])
+            raise _lib.ZcError(f"restore: bundle {b}: a chunk id twice in one bundle (entry {r.first_dup})")
+        p = RestorePlan()
+        p.data = backup_data
+        p.used = [int(b) for b in r.used]
+        p.pay_size = [int(s) for s in r.used_size]
+        aligned = (r.used_size + np.uint64(15)) & ~np.uint64(15)
+        ends = np.cumsum(aligned, dtype=np.uint64)
+        p.pay_off = [0] + [int(x) for x in ends[:-1]] if r.n_used else []
+        p.instr_off = int(ends[-1]) if r.n_used else 0
+        p.work_size = p.instr_off + len(backup_data)
+        base = np.array(p.pay_off + [p.instr_off], dtype=np.uint64)
+        p.slot, p.off = r.slot, r.off
+        p.src_off = base[r.slot] + r.off
+        p.sizes = r.size
+        p.dst_off = r.dst
+        p.length = r.length
         return p
 
     def replay(self, plan, d_work, d_out, out_cap):
@@ -285,19 +320,34 @@ class IndexedRestorer:
 
     def __init__(self, backup_data, bundles, device=0, ctx=None):
         plan = Restorer.plan(backup_data, bundles)
-        self.plan = plan
-        self._comp = BundleCompressor(device=device, ctx=ctx) if device is not None or ctx is not None else None
         pay_off = np.asarray(plan.pay_off, dtype=np.uint64)
         in_instr = plan.src_off >= np.uint64(plan.instr_off)
         k = np.searchsorted(pay_off, plan.src_off, side="right").astype(np.int64) - 1
         k[in_instr] = len(plan.used)
         base = np.concatenate([pay_off, [plan.instr_off]]).astype(np.uint64)
+        self._setup(plan, k, plan.src_off - base[k], device, ctx)
+
+    @classmethod
+    def from_index(cls, backup_data, chunk_index, device=0, ctx=None):
+        """The same from a resident ChunkIndex: Restorer.plan_index's plan,
+        whose fetched (slot, offset) arrays are the RangeIndex's entries as
+        they are.  `needs` and the payload calls speak in the index's bundle
+        numbers.  ctx None: the chunk index's context."""
+        self = cls.__new__(cls)
+        plan = Restorer.plan_index(backup_data, chunk_index)
+        if device is not None and ctx is None:
+            ctx = chunk_index._ctx
+        self._setup(plan, plan.slot, plan.off, device, ctx)
+        return self
+
+    def _setup(self, plan, k, off, device, ctx):
+        self.plan = plan
+        self._comp = BundleCompressor(device=device, ctx=ctx) if device is not None or ctx is not None else None
         self._slot_of = {b: i for i, b in enumerate(plan.used)}
         self._decoded = {}  # slot -> device buffer of a payload decoded here
         self._index = None
         try:
-            self._index = RangeIndex(list(plan.pay_size) + [len(plan.data)], k, plan.src_off - base[k], plan.sizes,
-                                     comp=self._comp)
+            self._index = RangeIndex(list(plan.pay_size) + [len(plan.data)], k, off, plan.sizes, comp=self._comp)
             self.size = self._index.total
             if self._comp is not None:
                 self._index.upload_slot(len(plan.used), plan.data)
