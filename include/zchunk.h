@@ -228,12 +228,15 @@ int zc_finish(zc_ctx* ctx);
  * 16-byte aligned; the call runs the whole pipeline and fills the records.
  * The context's stream is ordered after work already queued on the legacy
  * default stream (so a buffer just written there is read complete). */
+/* Runs on the context's stream after the work queued on the default stream so far; complete on return. */
 int zc_chunk_device(zc_ctx* ctx, const void* d_data, uint64_t n);
 
 /* stream in host memory (pinned for full speed): copied to HBM in 64 MiB
  * segments on a side stream, each segment scanned as soon as it has landed,
  * then the same pipeline as zc_chunk_device; the end-to-end form of
  * backup_creator.cc's loop, with the feed's copies overlapped with the work */
+/* A host form: it touches no caller device memory and is not ordered after the default stream;
+ * complete on return. */
 int zc_chunk_host(zc_ctx* ctx, const void* host, uint64_t n);
 
 size_t zc_record_count(const zc_ctx* ctx);  /* complete records held (cut, ids filled in, not yet taken) */
@@ -344,6 +347,7 @@ int zc_bundle_plan(const uint64_t* sizes, size_t n, uint64_t max_payload, uint32
                    size_t* n_bundles);
 /* Bundle::Creator::addChunk's payload (bundle.cc:30-36) on the device: chunk i's bytes
  * d_src[src_off[i] ..+ sizes[i]) appended to d_payload back to back (HBM to HBM). */
+/* Runs on the context's stream after the work queued on the default stream so far; complete on return. */
 int zc_bundle_gather(zc_ctx* ctx, const void* d_src, const uint64_t* src_off, const uint64_t* sizes,
                      size_t n, void* d_payload);
 /* The lzo1x_1 compression Bundle::Creator::write runs on each bundle's payload
@@ -354,11 +358,14 @@ int zc_bundle_gather(zc_ctx* ctx, const void* d_src, const uint64_t* src_off, co
  * to d_out + out_off[i], which must leave zc_lzo_capacity(pay_size[i]) bytes; out_size[i]
  * (host) receives their count.  The bytes equal what the reference writes for the payload. */
 uint64_t zc_lzo_capacity(uint64_t payload_size); /* LZO1X_1_Encoder::suggestOutputSize + 16 */
+/* Runs on the context's stream after the work queued on the default stream so far; complete on return. */
 int zc_lzo_compress(zc_ctx* ctx, const void* d_payload, const uint64_t* pay_off, const uint64_t* pay_size,
                     size_t n, void* d_out, const uint64_t* out_off, uint64_t* out_size);
 /* the same for payloads in host memory (copied to HBM, compressed, copied back to
  * out + out_off[i]): the form Bundle::Creator::write can call per finished bundle (or per
  * batch of them) without device buffers of its own */
+/* A host form: it touches no caller device memory and is not ordered after the default stream;
+ * complete on return. */
 int zc_lzo_compress_host(zc_ctx* ctx, const void* payload, const uint64_t* pay_off, const uint64_t* pay_size,
                          size_t n, void* out, const uint64_t* out_off, uint64_t* out_size);
 /* Adler-32 (zlib's adler32 from its initial value 1, as Adler32 wraps it: adler32.hh:13-33) of
@@ -367,6 +374,7 @@ int zc_lzo_compress_host(zc_ctx* ctx, const void* payload, const uint64_t* pay_o
  * BundleInfo and after the payload (encrypted_file.cc:248-300,336-340, bundle.cc:116,153):
  * the payload's share comes from here, joined to the running value with zlib's
  * adler32_combine(running, out[i], len[i]). */
+/* Runs on the context's stream after the work queued on the default stream so far; complete on return. */
 int zc_adler32(zc_ctx* ctx, const void* d_base, const uint64_t* off, const uint64_t* len, size_t n,
                uint32_t* out);
 /* device time of the last zc_lzo_compress's parse kernel (ms) and its 48 KiB blocks */
@@ -389,6 +397,7 @@ int zc_lzo_frame_info(const void* framed, size_t avail, uint64_t* payload_size, 
 /* The inverse of zc_bundle_gather (Bundle::Reader::get, bundle.cc:235-251, for every chunk a
  * restore emits): extent i, d_src[src_off[i] ..+ sizes[i]), goes to d_dst + dst_off[i].  One source
  * extent may go to many destinations (a chunk emitted more than once). */
+/* Runs on the context's stream after the work queued on the default stream so far; complete on return. */
 int zc_bundle_scatter(zc_ctx* ctx, const void* d_src, const uint64_t* src_off, const uint64_t* sizes,
                       size_t n, void* d_dst, const uint64_t* dst_off);
 /* One entry per chunk_to_emit / bytes_to_emit of a BackupInstruction stream, in the order
@@ -425,15 +434,21 @@ int zc_parse_instructions(const void* data, size_t n, zc_instruction* out, size_
  * i's output extent may be exactly its input extent (in place); any other overlap of an output
  * with an input is ZC_ERR_ARG.  Decrypt works on all blocks at once, so ANY overlap between an
  * input and an output extent is ZC_ERR_ARG. */
+/* Runs on the context's stream after the work queued on the default stream so far; complete on return. */
 int zc_aes128_cbc_encrypt(zc_ctx* ctx, const uint8_t key[16], const void* d_in, const uint64_t* in_off,
                           const uint64_t* len, size_t n, const uint8_t* iv, void* d_out, const uint64_t* out_off);
+/* Runs on the context's stream after the work queued on the default stream so far; complete on return. */
 int zc_aes128_cbc_decrypt(zc_ctx* ctx, const uint8_t key[16], const void* d_in, const uint64_t* in_off,
                           const uint64_t* len, size_t n, const uint8_t* iv, void* d_out, const uint64_t* out_off);
 /* the same for buffers in host memory (copied to HBM, run, copied back); the rules above hold
  * for the host extents, but the base pointers need no alignment */
+/* A host form: it touches no caller device memory and is not ordered after the default stream;
+ * complete on return. */
 int zc_aes128_cbc_encrypt_host(zc_ctx* ctx, const uint8_t key[16], const void* in, const uint64_t* in_off,
                                const uint64_t* len, size_t n, const uint8_t* iv, void* out,
                                const uint64_t* out_off);
+/* A host form: it touches no caller device memory and is not ordered after the default stream;
+ * complete on return. */
 int zc_aes128_cbc_decrypt_host(zc_ctx* ctx, const uint8_t key[16], const void* in, const uint64_t* in_off,
                                const uint64_t* len, size_t n, const uint8_t* iv, void* out,
                                const uint64_t* out_off);
@@ -469,9 +484,12 @@ typedef struct zc_bundle_file {
  * deterministic --, A1, the body copied HBM to HBM, A2, padding) and, with a key (NULL: none),
  * encrypts it in place.  file_size[i] (host) receives zc_bundle_file_size(...).  ZC_ERR_ARG: a
  * NULL pointer, a misaligned file_off or d_files, files that overlap each other. */
+/* Runs on the context's stream after the work queued on the default stream so far; complete on return. */
 int zc_bundle_seal(zc_ctx* ctx, const uint8_t* key, const void* prefix, const zc_bundle_file* files, size_t n,
                    const void* d_body, void* d_files, uint64_t* file_size);
 /* the same with bodies and files in host memory (the files are brought back to files + file_off) */
+/* A host form: it touches no caller device memory and is not ordered after the default stream;
+ * complete on return. */
 int zc_bundle_seal_host(zc_ctx* ctx, const uint8_t* key, const void* prefix, const zc_bundle_file* files, size_t n,
                         const void* body, void* files_out, uint64_t* file_size);
 
@@ -498,9 +516,12 @@ typedef struct zc_bundle_layout {
  * with the files), reads the two lengths, the stored Adler-32s and the padding on the device and
  * checks both Adler-32s (zc_adler32's kernel).  A bad file does not fail the call: it gets its
  * status in layout[i].  ZC_ERR_ARG: NULL pointers, and with a key misaligned offsets / bases. */
+/* Runs on the context's stream after the work queued on the default stream so far; complete on return. */
 int zc_bundle_unseal(zc_ctx* ctx, const uint8_t* key, const void* d_files, const uint64_t* file_off,
                      const uint64_t* file_size, size_t n, void* d_plain, const uint64_t* plain_off,
                      zc_bundle_layout* layout);
+/* A host form: it touches no caller device memory and is not ordered after the default stream;
+ * complete on return. */
 int zc_bundle_unseal_host(zc_ctx* ctx, const uint8_t* key, const void* files, const uint64_t* file_off,
                           const uint64_t* file_size, size_t n, void* plain, const uint64_t* plain_off,
                           zc_bundle_layout* layout);
@@ -622,10 +643,13 @@ int zc_gc_last_times(const zc_ctx* ctx, double* upload_ms, double* host_ms, doub
  * with neither status nor n_bad.  n == 0 is ZC_OK.  Callers detect these entry points by their
  * symbols (the ABI version stays 5). */
 enum { ZC_META_BAD_SHA1 = 1, ZC_META_BAD_ROLLING = 2, ZC_META_BAD_SIZE = 4 };
+/* Runs on the context's stream after the work queued on the default stream so far; complete on return. */
 int zc_chunk_meta_compute(zc_ctx* ctx, const void* d_payload, uint64_t payload_bytes, const uint64_t* off,
                           const uint32_t* size, size_t n, const zc_seed* expect, zc_chunk_meta* out,
                           uint8_t* status, size_t* n_bad);
 /* the same with the payload in host memory (copied to HBM first) */
+/* A host form: it touches no caller device memory and is not ordered after the default stream;
+ * complete on return. */
 int zc_chunk_meta_compute_host(zc_ctx* ctx, const void* payload, uint64_t payload_bytes, const uint64_t* off,
                                const uint32_t* size, size_t n, const zc_seed* expect, zc_chunk_meta* out,
                                uint8_t* status, size_t* n_bad);
@@ -726,9 +750,12 @@ typedef struct zc_index_set zc_index_set;
  * (an internal error).  ZC_TEST_INDEX_TILE=<bytes> and ZC_TEST_INDEX_WAVE_MIN=<bytes> in the
  * environment shrink the LDS tile and the length from which a BundleInfo gets a whole wave: tests
  * only. */
+/* Runs on the context's stream after the work queued on the default stream so far; complete on return. */
 int zc_index_load(zc_ctx* ctx, const uint8_t* key, const void* d_files, const uint64_t* file_off,
                   const uint64_t* file_size, size_t n, zc_index_set** set);
 /* the same with the files in host memory (one upload; the base needs no alignment) */
+/* A host form: it touches no caller device memory and is not ordered after the default stream;
+ * complete on return. */
 int zc_index_load_host(zc_ctx* ctx, const uint8_t* key, const void* files, const uint64_t* file_off,
                        const uint64_t* file_size, size_t n, zc_index_set** set);
 int zc_index_set_counts(const zc_index_set* set, uint64_t* n_files, uint64_t* n_bundles, uint64_t* n_records);
@@ -746,9 +773,12 @@ int zc_index_set_destroy(zc_index_set* set);
  * plaintext: add plain_off[i]).  status[i] receives ZC_INDEX_OK, _BAD_MESSAGE or _BAD_CHUNK_ID; a bad
  * BundleInfo contributes no records.  ids (cap x 24), sizes (cap) and bundle_first (n + 1) are
  * host arrays; *n_records = the records found, also when cap is too small (ZC_ERR_ARG). */
+/* Runs on the context's stream after the work queued on the default stream so far; complete on return. */
 int zc_bundle_info_parse(zc_ctx* ctx, const void* d_plain, const uint64_t* info_off, const uint64_t* info_len,
                          size_t n, uint8_t* ids, uint32_t* sizes, uint64_t cap, uint64_t* bundle_first,
                          uint8_t* status, uint64_t* n_records);
+/* A host form: it touches no caller device memory and is not ordered after the default stream;
+ * complete on return. */
 int zc_bundle_info_parse_host(zc_ctx* ctx, const void* plain, const uint64_t* info_off, const uint64_t* info_len,
                               size_t n, uint8_t* ids, uint32_t* sizes, uint64_t cap, uint64_t* bundle_first,
                               uint8_t* status, uint64_t* n_records);
@@ -892,10 +922,12 @@ typedef struct zc_xz_result {
  * `decoded` bytes of the range are unspecified.  ZC_ERR_ARG with a message, before any device work:
  * NULL pointers, output ranges that overlap.  No input range may touch an output range.  n == 0 is
  * ZC_OK and launches nothing.  Runs on the context's stream after the work queued on the default
- * stream so far, as the other bundle calls do. */
+ * stream so far, as the other bundle calls do; complete on return. */
 int zc_xz_decode(zc_ctx* ctx, const void* d_in, const uint64_t* in_off, const uint64_t* in_size, size_t n,
                  void* d_out, const uint64_t* out_off, const uint64_t* out_cap, zc_xz_result* res);
 /* the same with streams and payloads in host memory (one upload; the decoded bytes are copied back) */
+/* A host form: it touches no caller device memory and is not ordered after the default stream;
+ * complete on return. */
 int zc_xz_decode_host(zc_ctx* ctx, const void* in, const uint64_t* in_off, const uint64_t* in_size, size_t n,
                       void* out, const uint64_t* out_off, const uint64_t* out_cap, zc_xz_result* res);
 /* The context's last zc_xz_decode: time on the stream of the decode kernels (both forms) and of
@@ -937,11 +969,14 @@ typedef struct zc_xz_enc_result {
  * the status is ZC_XZ_OK; on ZC_XZ_E_OUTPUT the range's bytes are unspecified.  ZC_ERR_ARG with a
  * message, before any device work: NULL pointers, another check id, output ranges that overlap
  * each other or touch a payload, a payload of more than 64 MiB.  n == 0 is ZC_OK and launches
- * nothing.  Runs on the context's stream after the work queued on the default stream so far. */
+ * nothing.  Runs on the context's stream after the work queued on the default stream so far;
+ * complete on return. */
 int zc_xz_encode(zc_ctx* ctx, const void* d_payload, const uint64_t* pay_off, const uint64_t* pay_size, size_t n,
                  void* d_out, const uint64_t* out_off, const uint64_t* out_cap, uint32_t check,
                  zc_xz_enc_result* res);
 /* the same with payloads and streams in host memory (one upload; the streams are copied back) */
+/* A host form: it touches no caller device memory and is not ordered after the default stream;
+ * complete on return. */
 int zc_xz_encode_host(zc_ctx* ctx, const void* payload, const uint64_t* pay_off, const uint64_t* pay_size, size_t n,
                       void* out, const uint64_t* out_off, const uint64_t* out_cap, uint32_t check,
                       zc_xz_enc_result* res);
@@ -949,6 +984,18 @@ int zc_xz_encode_host(zc_ctx* ctx, const void* payload, const uint64_t* pay_off,
  * the check kernel (summed over the call's batches), and the whole call's wall clock. */
 int zc_xz_encode_last_stats(const zc_ctx* ctx, double* match_ms, double* code_ms, double* check_ms,
                             double* total_ms);
+/* Tests only.  The context's last zc_xz_encode: how many batches it was cut into (a launch of the
+ * match and of the coding kernel each), the most payloads a wave took in one launch (its rounds), and
+ * the hash tables' generation after it; all 0 before the first call.  A NULL output is skipped.
+ * Detected by symbol (the ABI version stays 5).  Two environment variables reach the schedule's
+ * edges, tests only as ZC_TEST_GC_BITS is: ZC_TEST_XZENC_POOL=<bytes>, read at every call, stands
+ * for the share of the free memory in a batch's room for candidates, which stays at least the
+ * largest payload (a batch is the longest run of payloads whose sizes fit it; anything that does
+ * not parse to at least 1 is ignored); ZC_TEST_XZENC_GEN0=<u32>, read when the context's encoder
+ * state is made (its first zc_xz_encode) and used only inside [0, 0xfffffffe], is the generation a
+ * fresh or regrown table starts from, so that the 32-bit generation's end is a few calls away;
+ * a table cleared because the generations ran out starts from 0 again. */
+int zc_xz_encode_last_schedule(const zc_ctx* ctx, uint64_t* batches, uint64_t* max_rounds, uint32_t* generation);
 
 int zc_abi_version(void);
 /* digest of the sources this library was built from (zbackup_amd/_build.py

@@ -275,7 +275,9 @@ def test_end_to_end(torch_cuda, comp):
 
 def test_read_host_follows_default_stream_work(torch_cuda, comp):
     """A caller-owned slot filled on the default stream and read straight away,
-    with no synchronisation in between: both forms of the read come after the fill."""
+    with no synchronisation in between: both forms of the read come after the fill.
+    The device form's destination has a fill queued over it as well: the read
+    lands on top of it, not under it."""
     from zbackup_amd import RangeIndex
     torch = torch_cuda
     n = 64 << 20
@@ -283,6 +285,7 @@ def test_read_host_follows_default_stream_work(torch_cuda, comp):
     filler = torch.empty(256 << 20, dtype=torch.uint8, device="cuda")
     d_slot = torch.zeros(n, dtype=torch.uint8, device="cuda")
     d_dst = torch.full((4096 + 32,), CANARY, dtype=torch.uint8, device="cuda")
+    snap = torch.zeros_like(d_dst)
     want = src[-4096:].cpu().numpy()
     with RangeIndex([n], [0], [0], [n], comp=comp) as index:
         index.set_slot(0, d_slot.data_ptr())
@@ -295,8 +298,14 @@ def test_read_host_follows_default_stream_work(torch_cuda, comp):
             if form == "host":
                 got = np.frombuffer(index.read_host([(n - 4096, 4096)])[0], dtype=np.uint8)
             else:
+                # the destination too: a fill queued over it and a reader of that fill, both before the read
+                d_dst.fill_(CANARY)
+                snap.copy_(d_dst)
                 index.read([(n - 4096, 4096)], d_dst.data_ptr(), [16])
-                got = d_dst.cpu().numpy()[16:-16]
+                assert bool((snap == CANARY).all()), "the read wrote under a reader queued before it"
+                whole = d_dst.cpu().numpy()
+                assert (whole[:16] == CANARY).all() and (whole[-16:] == CANARY).all()
+                got = whole[16:-16]
             assert np.array_equal(got, want), form
 
 

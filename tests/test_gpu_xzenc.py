@@ -57,6 +57,12 @@ def reference(host_exe, tmp_path_factory):
     return cases, res, by_check
 
 
+@pytest.fixture(autouse=True)
+def no_hooks(monkeypatch):
+    monkeypatch.delenv("ZC_TEST_XZENC_POOL", raising=False)
+    monkeypatch.delenv("ZC_TEST_XZENC_GEN0", raising=False)
+
+
 def encode(torch, comp, payloads, check=4, caps=None, seed=0):
     """One zc_xz_encode call: payloads packed at odd offsets, outputs between
     canaries.  Returns (results, [the cap bytes of each output])."""
@@ -176,6 +182,191 @@ def test_more_bundles_than_one_grid_pass(torch_cuda, comp, host_exe, tmp_path):
             assert s == want, j
             assert lzma.decompress(s) == payloads[j], j
         assert (len(s), zlib.crc32(s)) == (len(want), zlib.crc32(want)), j
+
+
+# ---- the schedule: batches and the tables' generations (ZC_TEST_XZENC_POOL / ZC_TEST_XZENC_GEN0) ----
+
+GEN_LAST = 0xfffffffe  # the last generation a launch may use
+
+
+def fresh(monkeypatch, gen0=None):
+    """A compressor of its own: the encoder's state, made by its first call, reads ZC_TEST_XZENC_GEN0."""
+    from zbackup_amd.bundle import BundleCompressor
+    if gen0 is not None:
+        monkeypatch.setenv("ZC_TEST_XZENC_GEN0", str(gen0))
+    return BundleCompressor()
+
+
+def cus_of(torch):
+    return torch.cuda.get_device_properties(0).multi_processor_count
+
+
+def mixed_payloads(cases, by_check):
+    """Some 40 payloads, the sizes mixed: grid cases of 0, 1, 2049, 65536 and
+    65537 bytes and payloads of 300 and 40000; the largest first and last,
+    empty ones before and behind it."""
+    kinds = ("text", "halfdup", "random", "period65", "alphabet4", "zeros")
+    grid = {(cases[k][0].rsplit("_", 1)[0], len(cases[k][2])): cases[k][2] for k in by_check[4]}
+    order = [65537, 0, 0, 65537, 1, 300, 2049, 40000, 0, 40000, 0, 65536, 1, 0, 2049, 300, 65536, 0, 65537, 0, 40000,
+             300, 300, 2049, 1, 65536, 0, 0, 65536, 40000, 2049, 2049, 1, 300, 65537, 0, 40000, 0, 1, 0, 65537]
+    out = []
+    for j, n in enumerate(order):
+        kind = kinds[j % len(kinds)]
+        out.append(grid[(kind, n)] if (kind, n) in grid else XI.payload(kind, n, 200 + j).tobytes())
+    assert sum(1 for j, n in enumerate(order) if (kinds[j % len(kinds)], n) in grid) >= 25
+    return out
+
+
+@pytest.fixture(scope="module")
+def mixed(reference, host_exe, tmp_path_factory):
+    """(payloads, {check: [(status, stored, stream)]}): the host core's streams, which know no batches."""
+    cases, _, by_check = reference
+    payloads = mixed_payloads(cases, by_check)
+    tmp = tmp_path_factory.mktemp("xzenc_mixed")
+    return payloads, {check: E.run(host_exe, tmp, [(check, p) for p in payloads])[0] for check in (0, 1, 4)}
+
+
+def assert_streams(res, outs, payloads, ref, check=4):
+    got = streams_of(res, outs)
+    for j, (s, r, p, (_, stored, want)) in enumerate(zip(got, res, payloads, ref)):
+        assert s == want, (j, len(p))
+        assert int(r["info"]) & 15 == check and int(r["info"]) >> 8 == stored, (j, len(p))
+        assert lzma.decompress(s) == p, (j, len(p))
+
+
+@pytest.mark.parametrize("room", [65537, 1])
+def test_a_call_cut_into_batches(torch_cuda, monkeypatch, reference, mixed, room):
+    """ZC_TEST_XZENC_POOL stands for the free memory's share, so a call of a
+    few hundred KiB is cut as one of many GiB would be: later batches begin at
+    first > 0, write their candidates from offset 0 of the buffer the batch
+    before used, and run under the next generation.  Room 65537: batches of
+    several payloads.  Room 1: the pool is the largest payload, and among
+    payloads of 0, 40000 and more bytes every non-empty one is a batch."""
+    cases, ref_all, by_check = reference
+    payloads, ref = mixed
+    keep = list(range(len(payloads))) if room == 65537 else [j for j, p in enumerate(payloads)
+                                                             if len(p) == 0 or len(p) >= 40000]
+    payloads = [payloads[j] for j in keep]
+    sizes = [len(p) for p in payloads]
+    assert sizes[0] == sizes[-1] == max(sizes) == 65537 and len(payloads) >= (40 if room == 65537 else 20)
+    ends = E.batch_ends(sizes, room)
+    assert len(ends) >= 5
+    cuts = ends[:-1]
+    assert any(sizes[e - 1] == 0 for e in cuts) and any(sizes[e + 1] == 0 for e in cuts)  # empty ones at a cut
+    if room == 1:
+        assert len(ends) == sum(1 for n in sizes if n)
+    # the grid's payloads among them are the module's reference too
+    known = {cases[k][2]: ref_all[k][2] for k in by_check[4]}
+    assert all(ref[4][j][2] == known[p] for j, p in zip(keep, payloads) if p in known)
+    monkeypatch.setenv("ZC_TEST_XZENC_POOL", str(room))
+    with fresh(monkeypatch) as c:
+        gen = 0
+        for check in (0, 1, 4):
+            res, outs, _ = encode(torch_cuda, c, payloads, check=check, seed=check + room)
+            assert_streams(res, outs, payloads, [ref[check][j] for j in keep], check)
+            st = c.xz_last_stats()
+            gen += len(ends)
+            print(room, check, st)
+            assert (st["batches"], st["max_rounds"], st["generation"]) == (len(ends), 1, gen)
+        # what does not parse is ignored: one batch, wider than any before, so on regrown tables
+        for bad in ("none", "0", "-5"):
+            monkeypatch.setenv("ZC_TEST_XZENC_POOL", bad)
+            res, outs, _ = encode(torch_cuda, c, payloads, seed=9)
+            assert_streams(res, outs, payloads, [ref[4][j] for j in keep])
+            st = c.xz_last_stats()
+            assert (st["batches"], st["max_rounds"]) == (1, 1), bad
+        assert st["generation"] == 3
+
+
+def test_the_last_generation_is_used_and_the_next_call_clears(torch_cuda, monkeypatch, mixed):
+    """A call whose last batch runs under generation 0xfffffffe exactly: no
+    clear.  The call after it starts over on cleared tables."""
+    payloads, ref = mixed
+    payloads, ref = payloads[:16], ref[4][:16]
+    ends = E.batch_ends([len(p) for p in payloads], 65537)
+    assert len(ends) >= 3
+    monkeypatch.setenv("ZC_TEST_XZENC_POOL", "65537")
+    with fresh(monkeypatch, GEN_LAST - len(ends)) as c:
+        res, outs, _ = encode(torch_cuda, c, payloads, seed=1)
+        assert_streams(res, outs, payloads, ref)
+        st = c.xz_last_stats()
+        assert (st["batches"], st["max_rounds"], st["generation"]) == (len(ends), 1, GEN_LAST)
+        assert E.generations(ends, cus_of(torch_cuda), GEN_LAST - len(ends)) == (GEN_LAST, [])
+        res, outs, _ = encode(torch_cuda, c, payloads, seed=2)
+        assert_streams(res, outs, payloads, ref)
+        st = c.xz_last_stats()
+        assert (st["batches"], st["generation"]) == (len(ends), len(ends))  # cleared before its first batch
+        assert E.generations(ends, cus_of(torch_cuda), GEN_LAST) == (len(ends), [0])
+
+
+def test_the_tables_are_cleared_in_the_middle_of_a_call(torch_cuda, monkeypatch, mixed):
+    payloads, ref = mixed
+    payloads, ref = payloads[:16], ref[4][:16]
+    ends = E.batch_ends([len(p) for p in payloads], 65537)
+    assert len(ends) >= 4
+    monkeypatch.setenv("ZC_TEST_XZENC_POOL", "65537")
+    gen0 = GEN_LAST - 2  # two batches fit, the third clears
+    assert E.generations(ends, cus_of(torch_cuda), gen0) == (len(ends) - 2, [2])
+    with fresh(monkeypatch, gen0) as c:
+        for turn in range(2):
+            res, outs, _ = encode(torch_cuda, c, payloads, seed=3 + turn)
+            assert_streams(res, outs, payloads, ref)  # the batches before the clear and after it
+            st = c.xz_last_stats()
+            assert (st["batches"], st["generation"]) == (len(ends), (turn + 1) * len(ends) - 2)
+        other = [XI.payload("text", 5000 + 17 * j, 50 + j).tobytes() for j in range(12)]
+        res, outs, _ = encode(torch_cuda, c, other, seed=7)
+        for s, p in zip(streams_of(res, outs), other):
+            assert lzma.decompress(s) == p
+
+
+def test_two_rounds_under_the_last_two_generations(torch_cuda, monkeypatch, host_exe, tmp_path):
+    """test_more_bundles_than_one_grid_pass's shape on a context whose launch
+    starts at generation 0xfffffffd: the waves' second payloads run under
+    0xfffffffe, the last one there is."""
+    torch = torch_cuda
+    waves = 2 * 4 * cus_of(torch)
+    n = waves + waves // 2 + 3
+    kinds = ("text", "halfdup", "alphabet4", "random", "period65")
+    payloads = [XI.payload(kinds[j % 5], 2048 - j % 7, 1000 + j).tobytes() for j in range(n)]
+    ref, _ = E.run(host_exe, tmp_path, [(4, p) for p in payloads])
+    with fresh(monkeypatch, GEN_LAST - 2) as c:  # the launch's first generation is the scratch's + 1
+        res, outs, _ = encode(torch, c, payloads, seed=3)
+        st = c.xz_last_stats()
+        assert (st["batches"], st["max_rounds"], st["generation"]) == (1, 2, GEN_LAST)
+        got = streams_of(res, outs)
+        pick = set(np.random.default_rng(5).choice(n, 64, replace=False).tolist()) | {0, waves - 1, waves, n - 1}
+        for j, (s, (_, stored, want)) in enumerate(zip(got, ref)):
+            if j in pick:
+                assert s == want, j
+                assert lzma.decompress(s) == payloads[j], j
+            assert (len(s), zlib.crc32(s)) == (len(want), zlib.crc32(want)), j
+        # one more round would pass the end: the same call again clears first
+        res, outs, _ = encode(torch, c, payloads[:waves // 4], seed=4)
+        assert streams_of(res, outs) == [r[2] for r in ref[:waves // 4]]
+        assert c.xz_last_stats()["generation"] == 1
+
+
+def test_regrown_tables_start_from_gen0(torch_cuda, monkeypatch, mixed):
+    """A small call, then one wide enough to take more tables: the new tables
+    are cleared and start from ZC_TEST_XZENC_GEN0 as the first ones did."""
+    payloads, ref = mixed
+    gen0 = 0x7fffffff
+    with fresh(monkeypatch, gen0) as c:
+        res, outs, _ = encode(torch_cuda, c, payloads[:4], seed=1)
+        assert_streams(res, outs, payloads[:4], ref[4][:4])
+        assert c.xz_last_stats()["generation"] == gen0 + 1
+        res, outs, _ = encode(torch_cuda, c, payloads, seed=2)  # 41 waves' tables instead of 4
+        assert_streams(res, outs, payloads, ref[4])
+        st = c.xz_last_stats()
+        assert (st["batches"], st["generation"]) == (1, gen0 + 1)
+        res, outs, _ = encode(torch_cuda, c, payloads[:4], seed=3)  # narrower again: the tables stay
+        assert_streams(res, outs, payloads[:4], ref[4][:4])
+        assert c.xz_last_stats()["generation"] == gen0 + 2
+    for bad in ("-1", str(0xffffffff), "x", ""):  # outside [0, 0xfffffffe]: not honoured
+        with fresh(monkeypatch, bad) as c:
+            res, outs, _ = encode(torch_cuda, c, payloads[:4], seed=1)
+            assert_streams(res, outs, payloads[:4], ref[4][:4])
+            assert c.xz_last_stats()["generation"] == 1, bad
 
 
 def test_room_one_byte_short(torch_cuda, comp, reference):

@@ -155,3 +155,28 @@ def test_smaller_than_lzo_on_two_mib(check_exe, tmp_path):
         assert status == R.OK and len(stream) <= E.capacity(len(data))
         if k != "random":
             assert len(stream) < lzo, k
+
+
+def test_the_model_of_the_cutting_rule():
+    """tests/xzenc_ref.py's restatement of how zc_xz_encode cuts a call into
+    batches (the GPU tests predict zc_xz_encode_last_schedule with it), against
+    cuts written out by hand."""
+    ends = E.batch_ends
+    assert ends([], 1) == [] and ends([], 1 << 40) == []                  # the empty call launches nothing
+    assert ends([0, 0, 0], 1) == [3]                                        # no bytes: one batch, never cut
+    assert ends([100], 1) == [1] and ends([100, 100], 1) == [1, 2]          # larger than the room: the pool grows to it
+    assert ends([10, 20, 30], 60) == [3]                                    # an exact fit
+    assert ends([10, 20, 30], 59) == [2, 3] and ends([10, 20, 30], 61) == [3]
+    assert ends([30, 30, 30, 30], 60) == [2, 4]
+    assert ends([5, 0, 0, 5], 5) == [3, 4]                                  # empty payloads never start a batch ...
+    assert ends([0, 0, 5, 0, 5, 0], 1) == [4, 6]                            # ... and never end one
+    assert ends([7, 1, 1, 1], 1) == [1, 4] and ends([1, 1, 1, 7], 1) == [3, 4]  # the pool is the largest payload
+    assert ends([65537, 0, 65536, 1, 0, 1], 65537) == [2, 5, 6]                # 65536 + 1 fits exactly
+    assert E.rounds_of(1, 256) == 1 and E.rounds_of(2048, 256) == 1 and E.rounds_of(2049, 256) == 2
+    assert E.rounds_of(5, 1) == 1 and E.rounds_of(9, 1) == 2 and E.rounds_of(3 * 8 + 1, 1) == 4
+    # generations: a batch a generation, the clear when the last one would reach 0xffffffff
+    assert E.generations([1, 2, 3], 256, 0) == (3, [])
+    assert E.generations([1, 2, 3], 256, 0xfffffffb) == (0xfffffffe, [])
+    assert E.generations([1, 2, 3], 256, 0xfffffffc) == (1, [2])
+    assert E.generations([1, 2, 3], 256, 0xfffffffe) == (3, [0])
+    assert E.generations([2049], 256, 0xfffffffc) == (0xfffffffe, []) and E.generations([2049], 256, 0xfffffffd) == (2, [0])

@@ -30,6 +30,8 @@ def test_null_context_is_an_argument_error(lib):
         assert rc == _lib.ZC_ERR_ARG
         assert b"null context" in lib.zc_last_error(None)
     assert lib.zc_xz_encode_last_stats(None, None, None, None, None) == _lib.ZC_ERR_ARG
+    assert lib.zc_xz_encode_last_schedule(None, None, None, None) == _lib.ZC_ERR_ARG
+    assert b"zc_xz_encode_last_schedule: null context" in lib.zc_last_error(None)
 
 
 def test_result_layout_matches_the_header():
@@ -91,4 +93,11 @@ def test_argument_errors_come_with_a_message_and_before_any_device_work(lib):
             # an empty call is fine whatever the pointers are, and launches nothing
             rc, msg = call(host=host, n=0, pay=None, out=None, r=None)
             assert rc == _lib.ZC_OK
-        assert bc.xz_last_stats() == dict(match_ms=0.0, code_ms=0.0, check_ms=0.0, total_ms=0.0)
+        assert bc.xz_last_stats() == dict(match_ms=0.0, code_ms=0.0, check_ms=0.0, total_ms=0.0, batches=0,
+                                          max_rounds=0, generation=0)
+        # every output of the schedule is optional, alone and together
+        b, r, g = ctypes.c_uint64(7), ctypes.c_uint64(7), ctypes.c_uint32(7)
+        assert L.zc_xz_encode_last_schedule(ctx, None, None, None) == _lib.ZC_OK
+        assert L.zc_xz_encode_last_schedule(ctx, ctypes.byref(b), None, None) == _lib.ZC_OK and b.value == 0
+        assert L.zc_xz_encode_last_schedule(ctx, None, ctypes.byref(r), None) == _lib.ZC_OK and r.value == 0
+        assert L.zc_xz_encode_last_schedule(ctx, None, None, ctypes.byref(g)) == _lib.ZC_OK and g.value == 0

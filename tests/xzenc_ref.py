@@ -68,6 +68,45 @@ def run(exe, tmp_path, cases, name="enc"):
     return res, kinds
 
 
+# ---- the schedule: zc_xzenc.hip's cutting rule and generations, restated ----
+
+GEN_END = 0xffffffff  # a launch whose last generation would reach this clears the tables first
+
+
+def batch_ends(sizes, room):
+    """Where xzenc_encode cuts a call: a batch is the longest run of payloads whose
+    sizes fit pool = max(largest payload, room).  The ends, one per batch."""
+    if not len(sizes):
+        return []
+    pool, ends, in_batch = max(max(sizes), 1, room), [], 0
+    for i, n in enumerate(sizes):
+        if in_batch and in_batch + n > pool:
+            ends.append(i)
+            in_batch = 0
+        in_batch += n
+    return ends + [len(sizes)]
+
+
+def rounds_of(count, cus):
+    """Payloads the busiest wave of a launch over `count` payloads takes."""
+    slots = 4 * max(1, min((count + 3) // 4, 2 * cus))
+    return (count + slots - 1) // slots
+
+
+def generations(ends, cus, gen):
+    """The generation after a call cut at `ends` that began at `gen`, and the
+    batches before which the tables were cleared (none regrown on the way)."""
+    cleared, lo = [], 0
+    for b, hi in enumerate(ends):
+        r = rounds_of(hi - lo, cus)
+        if gen + r >= GEN_END:
+            cleared.append(b)
+            gen = 0
+        gen += r
+        lo = hi
+    return gen, cleared
+
+
 # ---- the cases ----
 
 def _p(kind, n, seed):

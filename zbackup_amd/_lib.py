@@ -34,7 +34,7 @@ EXPORTS = ["zc_create", "zc_destroy", "zc_seed_index", "zc_get_input_buffer",
            "zc_index_set_destroy", "zc_bundle_info_parse", "zc_bundle_info_parse_host", "zc_index_serialize",
            "zc_index_file_size", "zc_index_last_stats",
            "zc_xz_decode", "zc_xz_decode_host", "zc_xz_last_stats", "zc_device_alloc", "zc_device_free", "zc_upload",
-           "zc_xz_capacity", "zc_xz_encode", "zc_xz_encode_host", "zc_xz_encode_last_stats",
+           "zc_xz_capacity", "zc_xz_encode", "zc_xz_encode_host", "zc_xz_encode_last_stats", "zc_xz_encode_last_schedule",
            "zc_chunk_index_create", "zc_chunk_index_create_arrays", "zc_chunk_index_counts", "zc_chunk_index_bundles",
            "zc_chunk_index_lookup", "zc_chunk_index_destroy", "zc_restore_resolve", "zc_restore_plan_counts",
            "zc_restore_plan_fetch", "zc_restore_plan_destroy", "zc_resolve_last_stats"]
@@ -285,6 +285,7 @@ def load(path=LIB_PATH):
         "zc_xz_encode": (i32, [vp, vp, vp, vp, sz, vp, vp, vp, u32, vp]),
         "zc_xz_encode_host": (i32, [vp, vp, vp, vp, sz, vp, vp, vp, u32, vp]),
         "zc_xz_encode_last_stats": (i32, [vp] + [ctypes.POINTER(ctypes.c_double)] * 4),
+        "zc_xz_encode_last_schedule": (i32, [vp, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u32)]),
         # resident chunk index: (ctx, set, &idx); (ctx, ids, sizes, n_records, bundle_first, n_bundles, &idx)
         "zc_chunk_index_create": (i32, [vp, vp, ctypes.POINTER(vp)]),
         "zc_chunk_index_create_arrays": (i32, [vp, vp, vp, u64, vp, u64, ctypes.POINTER(vp)]),

@@ -198,11 +198,17 @@ class BundleCompressor:
         return [out[int(o):int(o) + int(r["size"])].tobytes() for o, r in zip(out_off, res)]
 
     def xz_last_stats(self):
-        """dict(match_ms, code_ms, check_ms, total_ms) of the last compress_xz."""
+        """dict(match_ms, code_ms, check_ms, total_ms) of the last compress_xz, and
+        its schedule (zc_xz_encode_last_schedule): batches, max_rounds, generation."""
         v = [ctypes.c_double() for _ in range(4)]
         rc = self._L.zc_xz_encode_last_stats(self._ctx, *[ctypes.byref(x) for x in v])
         _check(self._L, self._ctx, rc, "zc_xz_encode_last_stats")
-        return dict(zip(("match_ms", "code_ms", "check_ms", "total_ms"), (x.value for x in v)))
+        st = dict(zip(("match_ms", "code_ms", "check_ms", "total_ms"), (x.value for x in v)))
+        b, r, g = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint32()
+        rc = self._L.zc_xz_encode_last_schedule(self._ctx, ctypes.byref(b), ctypes.byref(r), ctypes.byref(g))
+        _check(self._L, self._ctx, rc, "zc_xz_encode_last_schedule")
+        st.update(batches=b.value, max_rounds=r.value, generation=g.value)
+        return st
 
     def scatter(self, d_src, src_off, sizes, d_dst, dst_off):
         """The inverse of gather: extent i, d_src[src_off[i] ..+ sizes[i]), to

@@ -701,6 +701,8 @@ struct XzEncTimes {
 XzEncScratch* xzenc_scratch_new();
 void xzenc_scratch_free(XzEncScratch* s);
 const XzEncTimes* xzenc_times(const XzEncScratch* s);
+// the last call's batches, the most rounds one of its launches took, and the generation handed out last
+void xzenc_schedule(const XzEncScratch* s, uint64_t* batches, uint64_t* max_rounds, uint32_t* generation);
 uint64_t xzenc_capacity(uint64_t n);
 int xzenc_validate(const void* pay, const uint64_t* pay_off, const uint64_t* pay_size, size_t n, const void* out,
                    const uint64_t* out_off, const uint64_t* out_cap, uint32_t check, const zc_xz_enc_result* res,

@@ -5027,3 +5027,15 @@ int zc_xz_encode_last_stats(const zc_ctx* c, double* match_ms, double* code_ms, 
   if (total_ms) *total_ms = t.total_ms;
   return ZC_OK;
 }
+
+int zc_xz_encode_last_schedule(const zc_ctx* c, uint64_t* batches, uint64_t* max_rounds, uint32_t* generation) {
+  ZC_LOCK(c);
+  if (!c) return host_arg_error("zc_xz_encode_last_schedule: null context");
+  uint64_t b = 0, r = 0;
+  uint32_t g = 0;
+  if (c->xzenc) xzenc_schedule(c->xzenc, &b, &r, &g);
+  if (batches) *batches = b;
+  if (max_rounds) *max_rounds = r;
+  if (generation) *generation = g;
+  return ZC_OK;
+}

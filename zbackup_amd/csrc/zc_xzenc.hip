@@ -28,6 +28,7 @@
 #include <hip/hip_runtime.h>
 
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
@@ -304,19 +305,36 @@ struct XzEncScratch {
   Buf<zcxzenc::EncResult> res;
   Buf<uint64_t> tables;   // a table per wave of the match kernel's grid
   Buf<uint32_t> cand;     // a distance per payload byte of a batch
+  uint32_t gen0 = 0;      // the generation a fresh, regrown or just-cleared table starts from (0; tests: ZC_TEST_XZENC_GEN0)
   uint32_t gen = 0;       // the last generation handed out
   hipEvent_t ev[2] = {};
   int cus = 0;
   XzEncTimes times{};
+  uint64_t max_rounds = 0;  // the largest count of rounds a launch of the last call took
   ~XzEncScratch() {
     for (hipEvent_t e : ev)
       if (e) (void)hipEventDestroy(e);
   }
 };
 
-XzEncScratch* xzenc_scratch_new() { return new XzEncScratch(); }
+XzEncScratch* xzenc_scratch_new() {
+  XzEncScratch* s = new XzEncScratch();
+  // (ZC_TEST_XZENC_GEN0: tests start the 32-bit generation near its end, which a context
+  // otherwise reaches after some 2^32 launches' rounds; used only inside [0, 0xfffffffe])
+  const char* tg = getenv("ZC_TEST_XZENC_GEN0");
+  char* end = nullptr;
+  const unsigned long long tgv = tg ? strtoull(tg, &end, 10) : 0;
+  if (tg && end != tg && *end == 0 && *tg != '-' && tgv <= 0xfffffffeull) s->gen = s->gen0 = (uint32_t)tgv;
+  return s;
+}
 void xzenc_scratch_free(XzEncScratch* s) { delete s; }
 const XzEncTimes* xzenc_times(const XzEncScratch* s) { return &s->times; }
+
+void xzenc_schedule(const XzEncScratch* s, uint64_t* batches, uint64_t* max_rounds, uint32_t* generation) {
+  *batches = s->times.batches;
+  *max_rounds = s->max_rounds;
+  *generation = s->gen;
+}
 
 uint64_t xzenc_capacity(uint64_t n) { return zcxzenc::capacity(n); }
 
@@ -372,6 +390,7 @@ int xzenc_encode(XzEncScratch* s, bool host, const void* pay, const uint64_t* pa
                  zc_xz_enc_result* res, hipEvent_t ev_in, hipStream_t st, std::string& err) {
   const auto t_call = Clock::now();
   s->times = XzEncTimes{};
+  s->max_rounds = 0;
   if (!n) return ZC_OK;
   if (!s->cus) {
     int dev = 0, cus = 0;
@@ -416,7 +435,14 @@ int xzenc_encode(XzEncScratch* s, bool host, const void* pay, const uint64_t* pa
   for (size_t i = 0; i < n; i++) largest = std::max(largest, pay_size[i]);
   // four bytes of candidates per payload byte: at most a quarter of the free memory and 8 GiB,
   // and at least the largest payload's
-  const uint64_t pool = std::max<uint64_t>(largest, std::min<uint64_t>((uint64_t)free_b / 16, 2ull << 30));
+  // (ZC_TEST_XZENC_POOL=<bytes> stands for the second term: tests cut a small call into batches)
+  uint64_t room = std::min<uint64_t>((uint64_t)free_b / 16, 2ull << 30);
+  if (const char* tp = getenv("ZC_TEST_XZENC_POOL")) {
+    char* end = nullptr;
+    const unsigned long long v = strtoull(tp, &end, 10);
+    if (end != tp && *end == 0 && *tp != '-' && v >= 1) room = v;
+  }
+  const uint64_t pool = std::max<uint64_t>(largest, room);
   std::vector<EncDesc> desc(n);
   std::vector<size_t> batch_end;
   uint64_t in_batch = 0, most = 0;
@@ -441,7 +467,7 @@ int xzenc_encode(XzEncScratch* s, bool host, const void* pay, const uint64_t* pa
   if (slots * kTableEntries > s->tables.cap || !s->tables.p) {
     XCK(s->tables.ensure(slots * kTableEntries));
     XCK(hipMemsetAsync(s->tables.p, 0, slots * kTableEntries * sizeof(uint64_t), st));  // generation 0: no entry
-    s->gen = 0;
+    s->gen = s->gen0;
   }
   XCK(s->cand.ensure(most));
   XCK(s->desc.ensure(n));
@@ -472,6 +498,7 @@ int xzenc_encode(XzEncScratch* s, bool host, const void* pay, const uint64_t* pa
                        (uint32_t)count, s->tables.p, s->gen + 1, s->cand.p);
     XCK(hipGetLastError());
     s->gen += (uint32_t)rounds;
+    s->max_rounds = std::max(s->max_rounds, rounds);
     XCK(hipEventRecord(s->ev[1], st));
     XCK(hipEventSynchronize(s->ev[1]));
     XCK(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
