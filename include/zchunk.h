@@ -275,7 +275,8 @@ int zc_last_stream_paths(const zc_ctx* ctx, uint32_t* bits);
  *   keys[0, n_keys)           the grid keys the scan wrote (key i: chunk [i W, (i + 1) W) of the full
  *                             2 MiB tiles), while they are still the scan's: a stream of one epoch
  *                             (zc_stats.epochs == 1) whose epoch took them as they were; else n_keys = 0
- *   max_tiles_per_wave        the most wave-tiles one wave walked in a scan-kernel launch of the stream
+ *   max_tiles_per_wave        at least one wave walked this many wave-tiles in a scan-kernel launch of the
+ *                             stream: ceil(wave-tiles / waves) of the launch (waves claim their wave-tiles)
  * ZC_ERR_ARG with the counts set when an array is missing or too small (all capacities 0 asks for the
  * counts); ZC_ERR_STATE when a wave-tile is still marked overflowed, a directory entry points outside
  * its pool, or the pinned host copy of the keys differs from the device's (errors of the engine). */

@@ -35,7 +35,10 @@ int main(int argc, char** argv) {
     for (int v = 0; v < 2; ++v) {
       CK(hipMemset(cnt[v], 0, 64));
       CK(hipEventRecord(a));
-      if (v == 0) CK(launch_scan_tiles(d, n, 0, ntiles, anchor_lo_for(65536), blk[0], po, cnt[0], 0));
+      // (the claim counter: the last of the 8 words zeroed above, so base 0)
+      if (v == 0) CK(launch_scan_tiles(d, n, 0, ntiles, anchor_lo_for(65536), blk[0], po, cnt[0], 0,
+                                       GridKeysOut{nullptr, nullptr, 0, 0}, nullptr, nullptr, 0, nullptr,
+                                       ScanClaim{(uint32_t*)(cnt[0] + 7), 0}));
       else CK(gear32_scan(d, n, ntiles, blk[1], dbase, dcnt, prel, pg, wcap, cnt[1]));
       CK(hipEventRecord(b)); CK(hipEventSynchronize(b));
       float ms; CK(hipEventElapsedTime(&ms, a, b));

@@ -244,18 +244,32 @@ struct Cand {  // anchor-probe candidate: window ending at p may equal chunk ref
 enum { CNT_POOL = 0, CNT_OVERFLOW = 1, CNT_CAND = 2, CNT_RUNS = 3, CNT_FOVF = 4, CNT_ANCLESS = 5, CNT_CLASS = 6,
        CNT_PAIRS = 7, CNT_SPAIRS = 8, CNT_LAST = 9 };
 
+// The scan's wave-tile claims.  A wave's first wave-tile is fixed; every later
+// one it claims from *counter (one returning atomic per wave-tile processed),
+// so a launch over nwt wave-tiles adds exactly nwt to it.  The counter is
+// never cleared between launches: base is its value before the launch (the
+// caller keeps the running sum, modulo 2^32), and launches that share a
+// counter must not overlap.
+struct ScanClaim {
+  uint32_t* counter;
+  uint32_t base;
+};
+
 // --- launchers (return hipError_t of the launch) ---------------------------
 hipError_t launch_scan(const uint8_t* data, uint64_t n, int32_t anchor_lo, uint64_t* blk, PoolOut po,
-                       unsigned long long* counters, hipStream_t s);
+                       unsigned long long* counters, hipStream_t s, ScanClaim claim = ScanClaim{nullptr, 0});
 // the same in pieces: full 2 MiB tiles [tile0, tile0 + ntiles), then the
 // partial last tile (if any); the pieces may run as the stream arrives
 hipError_t launch_scan_tiles(const uint8_t* data, uint64_t n, uint64_t tile0, uint64_t ntiles, int32_t anchor_lo,
                              uint64_t* blk, PoolOut po, unsigned long long* counters, hipStream_t s,
                              GridKeysOut gko = GridKeysOut{nullptr, nullptr, 0, 0}, hipEvent_t start = nullptr,
-                             hipEvent_t stop = nullptr, uint32_t max_wgs = 0, uint32_t* tiles_per_wave = nullptr);
+                             hipEvent_t stop = nullptr, uint32_t max_wgs = 0, uint32_t* tiles_per_wave = nullptr,
+                             ScanClaim claim = ScanClaim{nullptr, 0});
 // (max_wgs: tests only, ZC_TEST_SCAN_WGS -- at most that many workgroups, so a
 // wave walks several wave-tiles on a stream of a few MiB; 0: no cap.
-// tiles_per_wave: receives the most wave-tiles one wave of this launch walks.)
+// tiles_per_wave: receives ceil(wave-tiles / waves) of this launch: at least
+// one wave walks that many.  claim: required (a null counter is
+// hipErrorInvalidValue) unless the kernel is built with the static partition.)
 // the W for which the scan can write the grid keys (GridKeysOut), else 0
 inline uint32_t scan_key_lshift_or_none(uint32_t W, bool& ok) {
   ok = W >= (uint32_t)ZC_LSPAN && W % ZC_LSPAN == 0 && ((64u * ZC_LSPAN) % W) == 0;

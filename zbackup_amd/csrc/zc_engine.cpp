@@ -559,8 +559,14 @@ struct zc_ctx {
   // the scan's own two counters (anchors pooled, wave-tiles overflowed), zero
   // between scans: the first epoch's chunk-metadata kernel hands them to
   // h_scnt and clears them (no copy behind the scan, no fill before the next)
+  // Word 2 (its low half) is the scan's wave-tile claim counter: zeroed with
+  // the others when the context is new or a stream failed, then never cleared;
+  // every scan launch adds its wave-tile count, and claim_base is the running
+  // sum the next launch starts from (modulo 2^32).  The hand-off copies it
+  // along, and scan_check compares it with the sum at the hand-off.
   DevBuf<unsigned long long> scnt;
   bool scnt_dirty = true;  // unknown contents (new, or a stream that failed): clear first
+  uint32_t claim_base = 0;
   DevBuf<uint8_t> gsha;  // SHA-1 of the first epoch's grid chunks (ZC_FLAG_SHA1)
   HostBuf<uint2> h_pairs;  // an epoch's pairs of grid chunks joined by speculation
   HostBuf<uint8_t> h_gsha;  // ... copied back on the SHA-1 stream right behind the kernel
@@ -910,7 +916,9 @@ class Resolver {
       hipEvent_t stop = last ? scan_end_event() : nullptr;
       uint32_t tpw = 0;
       HCK(launch_scan_tiles(d_, n_, tiles_done_, t1 - tiles_done_, anchor_lo_, blk_v(), pool_out(), c_.scnt.p,
-                            c_.stream, gko, start, stop, c_.test_scan_wgs, &tpw));
+                            c_.stream, gko, start, stop, c_.test_scan_wgs, &tpw,
+                            ScanClaim{(uint32_t*)(c_.scnt.p + 2), c_.claim_base}));
+      c_.claim_base += (uint32_t)((t1 - tiles_done_) * (ZC_SCAN_TPB / 64));
       scan_tpw_ = std::max(scan_tpw_, tpw);
       scan_end_recorded_ = stop != nullptr;
       tiles_done_ = t1;
@@ -1344,10 +1352,11 @@ class Resolver {
       HCK(hipMemsetAsync(c_.counters.p, 0, CNT_LAST * sizeof(unsigned long long), c_.stream));
     }
     c_.h_cnt.ensure(CNT_LAST);
-    c_.scnt.ensure(2);
+    c_.scnt.ensure(3);
     c_.h_scnt.ensure(CNT_LAST);
-    if (c_.scnt_dirty) {
-      HCK(hipMemsetAsync(c_.scnt.p, 0, 2 * sizeof(unsigned long long), c_.stream));
+    if (c_.scnt_dirty) {  // (the claim counter and its base start over too)
+      HCK(hipMemsetAsync(c_.scnt.p, 0, 3 * sizeof(unsigned long long), c_.stream));
+      c_.claim_base = 0;
       c_.scnt_dirty = false;
     }
   }
@@ -1375,7 +1384,9 @@ class Resolver {
   void scan_counters_readback() {
     if (!scnt_pending_) return;
     scnt_pending_ = false;
-    d2h(c_, c_.h_scnt.p, c_.scnt.p, 2);
+    claim_expect_ = c_.claim_base;
+    claim_handed_ = true;
+    d2h(c_, c_.h_scnt.p, c_.scnt.p, 3);
     HCK(hipMemsetAsync(c_.scnt.p, 0, 2 * sizeof(unsigned long long), c_.stream));
   }
 
@@ -1397,6 +1408,12 @@ class Resolver {
     scan_open_ = false;
     const uint64_t wt_lo = chk_wt_, wt_hi = nwt_done();
     chk_wt_ = wt_hi;
+    // every scan launch up to the hand-off claimed exactly its wave-tiles
+    if (claim_handed_ && (uint32_t)c_.h_scnt[2] != claim_expect_) {
+      c_.scnt_dirty = true;
+      throw ZcError{ZC_ERR_STATE, "internal error: the scan's wave-tile claims do not add up"};
+    }
+    claim_handed_ = false;
     const uint64_t found = c_.h_scnt[CNT_POOL];
     npool_ += found;
     c_.stats.anchors += found;
@@ -1440,6 +1457,8 @@ class Resolver {
   }
   bool scan_checked_ = true;
   bool scnt_pending_ = false;  // scans queued whose counters are still on the device
+  uint32_t claim_expect_ = 0;  // the claim counter's value at the last hand-off of the counters
+  bool claim_handed_ = false;  // a hand-off since the last scan_check
   bool meta_from_scan_ = false;  // ev1 marks the end of scan launches queued for this batch
   hipEvent_t side_wait_ = nullptr;  // the copy stream's next work waits for this scan end
   hipEvent_t scan_end_ev_ = nullptr;  // recorded at the last scan's end (scan_finish)
@@ -1550,6 +1569,8 @@ class Resolver {
           ix.scnt = c_.scnt.p;
           ix.h_scnt = c_.h_scnt.p;
           scnt_pending_ = false;
+          claim_expect_ = c_.claim_base;
+          claim_handed_ = true;
         }
         grec_valid_ = false;
         grec_ = !windowed_ && indexable_ && nsref >= kGridRecordsMin;

@@ -203,8 +203,12 @@ __device__ __forceinline__ uint32_t load4_any(const uint8_t* base, uint64_t addr
 // groups); odd lanes take the two halves of their span in the other order (a
 // row stride of 4 KiB alone cost the staging 12 %).  The 32 bytes before each
 // half span (the anchor state's warm-up) are two register loads issued with
-// the DMA of the half's first round.  Waves never touch each other's LDS: no
-// barriers.  (DESIGN 4.1 has the measured geometry experiments 1-22.)
+// the DMA of the half's first round -- except before an even lane's second
+// half, which follows its first: its state rolls on.  A wave's first wave-tile
+// is fixed; each later one it claims from a device counter while it hashes the
+// one before (kScanClaim), so no wave idles while others still hold tiles.
+// Waves never touch each other's LDS: no barriers.  (DESIGN 4.1 has the
+// measured geometry experiments 1-24.)
 //
 // Anchors are appended to a per-wave LDS list (one ballot per 16-byte piece; a
 // wave-uniform block in the ~22 % of pieces where any lane hits) and moved to
@@ -489,9 +493,15 @@ __device__ __forceinline__ void stage_round(const uint8_t* __restrict__ data, ui
                                             const uint32_t (&lane_off)[kDmaRound], uint64_t tile, int r,
                                             uint32_t slot) {
   uint8_t* dst = ring + slot * (64 * ZC_ROUND);
-  const uint64_t at = kContigProbe
-                          ? tile * ZC_STILE + (uint64_t)wave * 64 * ZC_LSPAN + (uint64_t)r * 64 * ZC_ROUND
-                          : tile * ZC_STILE + (uint64_t)wave * 64 * ZC_LSPAN + (uint64_t)(r % kHalfRounds) * ZC_ROUND;
+  const uint64_t at_u = kContigProbe
+                            ? tile * ZC_STILE + (uint64_t)wave * 64 * ZC_LSPAN + (uint64_t)r * 64 * ZC_ROUND
+                            : tile * ZC_STILE + (uint64_t)wave * 64 * ZC_LSPAN +
+                                  (uint64_t)((uint32_t)r & (uint32_t)(kHalfRounds - 1)) * ZC_ROUND;
+  // (said to be wave-uniform in so many words: a descriptor the compiler takes
+  // for divergent costs a readfirstlane loop around every DMA instruction)
+  // (the builtin returns int: without the casts the low word is sign-extended)
+  const uint64_t at = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(at_u >> 32)) << 32) |
+                      (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)at_u);
   const auto rs = __builtin_amdgcn_make_buffer_rsrc((void*)(data + at), (short)0, 64 * ZC_LSPAN, 0x00020000);
   const uint32_t flip = !kContigProbe && r >= kHalfRounds ? kHalfSpan : 0u;
 #pragma unroll
@@ -730,7 +740,10 @@ __device__ __forceinline__ uint32_t scan_tile_end(uint64_t span0, uint32_t lane,
 }
 
 // Every wave walks whole wave-tiles (256 KiB, 64 lane spans) on its own:
-// wave-tiles wt0 + g, wt0 + g + G, ... for global wave g of G.  Its rounds form
+// wave-tile wt0 + g first for global wave g of G, then wave-tiles wt0 + G + c
+// for each claim c it draws from the launch's counter (kScanClaim; without it
+// wt0 + g + G, wt0 + g + 2 G, ...).  Every output is indexed by position, so
+// it does not matter which wave takes a wave-tile.  Its rounds form
 // one flat sequence over them (32 per wave-tile).  The ring has ONE slot per
 // wave: a round is read from the slot into registers, the slot is refilled
 // with the next round, then the round is hashed -- one round (8 KiB) in flight
@@ -742,7 +755,8 @@ __device__ __forceinline__ uint32_t scan_tile_end(uint64_t span0, uint32_t lane,
 // interleaved runs, outputs identical; experiment 21).  The 32 bytes before
 // each half of a lane span (they prime the anchor state) are two per-lane
 // register loads issued with the DMA of the half's first round, so half and
-// wave-tile boundaries cost no extra pipeline round.
+// wave-tile boundaries cost no extra pipeline round (even lanes load none
+// before their second half: kScanRoll).
 constexpr int kScanWaves = ZC_SCAN_WAVES;  // per workgroup (one per SIMD)
 #ifndef ZC_SCAN_WG_PER_CU_CFG
 #define ZC_SCAN_WG_PER_CU_CFG 2
@@ -763,6 +777,42 @@ constexpr int kScanSlots = ZC_SCAN_SLOTS_CFG;
 #endif
 constexpr int kScanPrioHandoff = ZC_SCAN_PRIO_CFG;
 static_assert(kScanSlots == 1 || kScanSlots == 2, "one or two ring slots");
+// Wave-tiles after a wave's first are claimed from one device counter (1), or
+// walked with the static stride of the launch's wave count (0: the A/B's
+// parent).  A static partition ends with the slowest wave while the others'
+// slots stand empty (experiment 23).
+#ifndef ZC_SCAN_CLAIM_CFG
+#define ZC_SCAN_CLAIM_CFG 1
+#endif
+constexpr bool kScanClaim = ZC_SCAN_CLAIM_CFG != 0;
+static_assert(!kScanClaim || kScanSlots == 1, "the claim is prefetched one tile ahead: one ring slot");
+// the round whose DMA group carries the claim for the next wave-tile (no
+// half's first round: those carry the warm-up loads); pinned one round later
+constexpr int kClaimRound = 8;
+// An even lane's second half follows its first, so its anchor state at the
+// half boundary already is the primed state: it keeps it and loads no warm-up
+// bytes there (1), or every lane re-primes at both halves (0: the A/B's
+// parent).  (experiment 24.)
+#ifndef ZC_SCAN_ROLL_CFG
+#define ZC_SCAN_ROLL_CFG 1
+#endif
+constexpr bool kScanRoll = ZC_SCAN_ROLL_CFG != 0;
+// tools/ubench/scan_geom_ab only (never set in the product): every wave
+// leaves its start and end clock, hardware ids and tile count at its exit
+#ifndef ZC_SCAN_STAMP_CFG
+#define ZC_SCAN_STAMP_CFG 0
+#endif
+#if ZC_SCAN_STAMP_CFG
+__device__ uint32_t* g_scan_stamp;  // 8 words per wave of the launch, or null
+#endif
+// one returning vector-memory atomic; the caller's hand-counted wait covers
+// the result (written as inline asm for the reason global_read16 is)
+__device__ __forceinline__ uint32_t claim_issue(uint32_t* counter) {
+  uint32_t v;
+  const uint32_t one = 1;
+  asm volatile("global_atomic_add %0, %1, %2, off sc0" : "=v"(v) : "v"(counter), "v"(one) : "memory");
+  return v;
+}
 struct ScanLds {
   uint8_t ring[kScanWaves][kScanSlots * 64 * ZC_ROUND];
   uint4 wdata[kScanWaves][ZC_WLIST];
@@ -772,15 +822,28 @@ static_assert(kScanWgPerCu * sizeof(ScanLds) <= 160 * 1024, "the scan workgroups
 __device__ __forceinline__ void scan_body(
     const uint8_t* __restrict__ data, uint64_t n, uint64_t wt0, uint64_t nwt, int32_t lo_thr,
     uint64_t* __restrict__ blk, PoolOut po, unsigned long long* __restrict__ counters, ScanLds& L,
-    GridKeysOut gko = GridKeysOut{nullptr, nullptr, 0, 0}) {
+    GridKeysOut gko = GridKeysOut{nullptr, nullptr, 0, 0}, ScanClaim claim = ScanClaim{nullptr, 0}) {
   constexpr uint32_t kRpt = kRounds;  // rounds per wave-tile
   constexpr uint32_t kWpt = ZC_SCAN_TPB / 64;  // wave-tiles per 2 MiB tile
   const uint32_t tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const uint32_t gw = blockIdx.x * kScanWaves + wave, nw = gridDim.x * kScanWaves;
   uint8_t* myring = L.ring[wave];
   WaveList wl{L.wlist[wave], L.wdata[wave], 0};
-  const uint32_t ntk = nwt > gw ? (uint32_t)((nwt - 1 - gw) / nw + 1) : 0;
-  const uint32_t nR = ntk * kRpt;
+#if ZC_SCAN_STAMP_CFG
+  const uint64_t stamp_t0 = wall_clock64();
+#endif
+  // the wave-tiles of this wave: the k-th is wt0 + gw + k * nw, or with the
+  // claim the first is wt0 + gw and each later one is claimed while the one
+  // before it is hashed (wt_nxt, known from round kClaimRound + 1 on), so the
+  // number of rounds grows as claims succeed
+  const uint32_t ntk = kScanClaim ? (nwt > gw ? 1u : 0u) : nwt > gw ? (uint32_t)((nwt - 1 - gw) / nw + 1) : 0;
+  uint32_t nR = ntk * kRpt;
+  uint64_t wt_cur = wt0 + gw, wt_nxt = 0;  // (claim) wave-uniform
+  uint32_t kc = 0;                         // (claim) wt_cur is the wave's kc-th tile
+  uint32_t claim_v = 0;                    // lane 0: the claim in flight
+  auto tile_of = [&](uint32_t k) -> uint64_t {
+    return kScanClaim ? (k == kc ? wt_cur : wt_nxt) : wt0 + gw + (uint64_t)k * nw;
+  };
   // this lane's share of DMA instruction j: row j * (1024 / ZC_ROUND) + lane /
   // kPieces of the wave, the source piece that lands at position lane % kPieces
   uint32_t lane_off[kDmaRound];
@@ -799,14 +862,17 @@ __device__ __forceinline__ void scan_body(
   auto group = [&](uint32_t Rx) -> uint32_t { return kDmaRound + ((Rx % kRpt) % kHalfRounds == 0 ? 2u : 0u); };
   auto issue = [&](uint32_t Rx) {
     const uint32_t k = Rx / kRpt, r = Rx - k * kRpt;
-    const uint64_t wt = wt0 + gw + (uint64_t)k * nw;
+    const uint64_t wt = tile_of(k);
     stage_round<kScanDmaAux>(data, myring, (uint32_t)(wt % kWpt), lane_off, wt / kWpt, (int)r, Rx % kScanSlots);
     if (r % kHalfRounds == 0) {
       // span 0 of the stream has no bytes before it: it reads itself (unused)
       const uint64_t at = (wt << ZC_WT_SHIFT) + (uint64_t)lane * ZC_LSPAN + (uint64_t)(r ^ hs) * ZC_ROUND;
       const uint8_t* src = at >= 32 ? data + at - 32 : data + at;
-      warm[0] = global_read16(src);
-      warm[1] = global_read16(src + 16);
+      // (an even lane's second half needs none: its state rolls on)
+      if (!kScanRoll || r == 0 || (lane & 1)) {
+        warm[0] = global_read16(src);
+        warm[1] = global_read16(src + 16);
+      }
     }
   };
   // after[i]: vector-memory instructions issued after the group of round
@@ -847,7 +913,11 @@ __device__ __forceinline__ void scan_body(
     const uint32_t pr = (uint32_t)r ^ hs;  // the physical round in the lane span
     if (r == 0) {
       // a new wave-tile
-      span0 = ((wt0 + gw + (uint64_t)k * nw) << ZC_WT_SHIFT) + (uint64_t)lane * ZC_LSPAN;
+      if (kScanClaim && k != kc) {
+        wt_cur = wt_nxt;
+        kc = k;
+      }
+      span0 = (tile_of(k) << ZC_WT_SHIFT) + (uint64_t)lane * ZC_LSPAN;
       s = ScanLane{0, 0, 0};
       wl.n = 0;
       last = kNoEntry;
@@ -856,13 +926,25 @@ __device__ __forceinline__ void scan_body(
       // a new half: the warm-up bytes prime the anchor state (it depends on
       // the 32 bytes before only, so this equals the state rolled on
       // continuously)
-      s.glo = 0;
       ties(warm);  // landed: the wait above covers them
+      uint32_t g = 0;
       if (span0 + pr * ZC_ROUND >= 64) {
         const uint32_t xs[8] = {warm[0][0], warm[0][1], warm[0][2], warm[0][3],
                                 warm[1][0], warm[1][1], warm[1][2], warm[1][3]};
 #pragma unroll
-        for (int j = 0; j < 8; ++j) s.glo = pk_step(pk_step(s.glo, bytes01(xs[j]), two), bytes23(xs[j]), two);
+        for (int j = 0; j < 8; ++j) g = pk_step(pk_step(g, bytes01(xs[j]), two), bytes23(xs[j]), two);
+      }
+      // (an even lane's second half: the state rolled on is the primed state)
+      s.glo = kScanRoll && r != 0 && !(lane & 1) ? s.glo : g;
+    }
+    if (kScanClaim && r == kClaimRound + 1) {
+      // the claim issued a round ago has landed (the wait above covers it):
+      // the wave's next wave-tile, if the launch still has one
+      asm volatile("" : "+v"(claim_v)::"memory");
+      const uint32_t c = __builtin_amdgcn_readfirstlane(claim_v) - claim.base;
+      if ((uint64_t)c + nw < nwt) {
+        wt_nxt = wt0 + nw + c;
+        nR += kRpt;
       }
     }
     // the round's pieces, in groups of four (one ties() each)
@@ -885,6 +967,8 @@ __device__ __forceinline__ void scan_body(
       for (int i = 0; i + 1 < kScanSlots; ++i) after[i] += group(R + kScanSlots);
       issue(R + kScanSlots);
     }
+    // every wave-tile claims once (the launch adds exactly nwt to the counter)
+    if (kScanClaim && r == kClaimRound && lane == 0) claim_v = claim_issue(claim.counter);
     if constexpr (kScanPrioHandoff > 0) __builtin_amdgcn_s_setprio(0);
 #pragma unroll
     for (int g = 0; g < kGroups; ++g)
@@ -909,14 +993,25 @@ __device__ __forceinline__ void scan_body(
     if (acc_pool) atomicAdd(&counters[CNT_POOL], (unsigned long long)acc_pool);
     if (acc_over) atomicAdd(&counters[CNT_OVERFLOW], (unsigned long long)acc_over);
   }
+#if ZC_SCAN_STAMP_CFG
+  if (lane == 0 && g_scan_stamp) {
+    const uint64_t t1 = wall_clock64();
+    // HW_ID (register 4) and XCC_ID (register 20), all 32 bits each
+    const uint32_t hw = __builtin_amdgcn_s_getreg(4 | (31 << 11)), xcc = __builtin_amdgcn_s_getreg(20 | (31 << 11));
+    uint4* o = (uint4*)(g_scan_stamp + 8 * gw);
+    o[0] = make_uint4((uint32_t)stamp_t0, (uint32_t)(stamp_t0 >> 32), (uint32_t)t1, (uint32_t)(t1 >> 32));
+    o[1] = make_uint4(hw, xcc, nR / kRpt, gw);
+  }
+#endif
 }
 
 // (__launch_bounds__' second argument: at least kScanWgPerCu waves per SIMD)
 __global__ void __launch_bounds__(64 * kScanWaves, kScanWgPerCu) zc_scan_kernel(
     const uint8_t* __restrict__ data, uint64_t n, uint64_t wt0, uint64_t nwt, int32_t lo_thr,
-    uint64_t* __restrict__ blk, PoolOut po, unsigned long long* __restrict__ counters, GridKeysOut gko) {
+    uint64_t* __restrict__ blk, PoolOut po, unsigned long long* __restrict__ counters, GridKeysOut gko,
+    ScanClaim claim) {
   __shared__ ScanLds lds;
-  scan_body(data, n, wt0, nwt, lo_thr, blk, po, counters, lds, gko);
+  scan_body(data, n, wt0, nwt, lo_thr, blk, po, counters, lds, gko, claim);
 }
 // the stream's last, partial tile: one 256-thread block per wave-tile, a
 // 1 KiB sub-span per thread (block digests and anchors)
@@ -1108,6 +1203,7 @@ __global__ void zc_chunk_meta_kernel(const uint8_t* __restrict__ data, uint64_t 
     ec.h_scnt[gt] = ec.scnt[gt];
     ec.scnt[gt] = 0ull;
   }
+  if (ec.scnt && gt == 2) ec.h_scnt[2] = ec.scnt[2];  // the scan's claim counter: read, never cleared
   if (gt < nchunks) {
     const uint32_t i = (uint32_t)gt;
     const uint64_t c = r_e + (uint64_t)i * W;
@@ -3041,9 +3137,11 @@ static int cu_count() {
 hipError_t launch_scan_tiles(const uint8_t* data, uint64_t n, uint64_t tile0, uint64_t ntiles, int32_t anchor_lo,
                              uint64_t* blk, PoolOut po, unsigned long long* counters, hipStream_t s,
                              GridKeysOut gko, hipEvent_t start, hipEvent_t stop, uint32_t max_wgs,
-                             uint32_t* tiles_per_wave) {
+                             uint32_t* tiles_per_wave, ScanClaim claim) {
   if (tiles_per_wave) *tiles_per_wave = 0;
   if (!ntiles) return hipSuccess;
+  // (the claim counter: the launch adds exactly its wave-tile count to it)
+  if (kScanClaim && (!claim.counter || ntiles * (ZC_SCAN_TPB / 64) > 0xFFFFFFFFull)) return hipErrorInvalidValue;
   if (gko.key && (!gko.hkey || ((uint64_t)ZC_LSPAN << gko.lshift) > (1ull << ZC_WT_SHIFT))) return hipErrorInvalidValue;
   // the tiles' wave-tiles, a wave each at a time, kScanWgPerCu workgroups per CU
   const uint64_t wt0 = tile0 * (ZC_SCAN_TPB / 64), nwt = ntiles * (ZC_SCAN_TPB / 64);
@@ -3051,14 +3149,15 @@ hipError_t launch_scan_tiles(const uint8_t* data, uint64_t n, uint64_t tile0, ui
                                                (uint64_t)cu_count() * kScanWgPerCu);
   // (a cap above the grid changes nothing, so values past 2 x CUs are ignored)
   if (max_wgs && max_wgs < grid) grid = max_wgs;
-  // wave 0 walks wave-tiles 0, G, 2 G, ... of the launch: the most of any wave
+  // at least one wave walks this many (with the static stride wave 0 does:
+  // wave-tiles 0, G, 2 G, ... of the launch; with the claim by pigeonhole)
   if (tiles_per_wave) *tiles_per_wave = (uint32_t)((nwt - 1) / ((uint64_t)grid * kScanWaves) + 1);
   if (start || stop)
     hipExtLaunchKernelGGL(zc_scan_kernel, dim3(grid), dim3(64 * kScanWaves), 0, s, start, stop, 0, data, n, wt0, nwt,
-                          anchor_lo, blk, po, counters, gko);
+                          anchor_lo, blk, po, counters, gko, claim);
   else
     hipLaunchKernelGGL(zc_scan_kernel, dim3(grid), dim3(64 * kScanWaves), 0, s, data, n, wt0, nwt, anchor_lo, blk,
-                       po, counters, gko);
+                       po, counters, gko, claim);
   return hipGetLastError();
 }
 
@@ -3076,8 +3175,9 @@ hipError_t launch_scan_tail(const uint8_t* data, uint64_t n, int32_t anchor_lo, 
 }
 
 hipError_t launch_scan(const uint8_t* data, uint64_t n, int32_t anchor_lo, uint64_t* blk, PoolOut po,
-                       unsigned long long* counters, hipStream_t s) {
-  hipError_t e = launch_scan_tiles(data, n, 0, n / ZC_STILE, anchor_lo, blk, po, counters, s);
+                       unsigned long long* counters, hipStream_t s, ScanClaim claim) {
+  hipError_t e = launch_scan_tiles(data, n, 0, n / ZC_STILE, anchor_lo, blk, po, counters, s,
+                                   GridKeysOut{nullptr, nullptr, 0, 0}, nullptr, nullptr, 0, nullptr, claim);
   if (e != hipSuccess) return e;
   return launch_scan_tail(data, n, anchor_lo, blk, po, counters, s);
 }
