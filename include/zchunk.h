@@ -60,6 +60,9 @@
  *   zc_xz_decode           LZMADecoder under Bundle::Reader, many bundles a call
  *   zc_xz_encode           LZMAEncoder under Bundle::Creator, many bundles a call
  *                                                      compression.cc:99-107, bundle.cc:179-216
+ *   zc_parse_instructions_device, zc_restore_resolve_device, zc_restore_replay
+ *                          one round of BackupRestorer::restoreIterations with the stream, its
+ *                          entries and the plan in HBM                 backup_restorer.cc:109-136
  *   zc_device_alloc, zc_device_free, zc_upload
  *                          no counterpart: device memory for callers that have no HIP binding
  *                          of their own and keep decoded payloads in HBM
@@ -849,8 +852,8 @@ int zc_chunk_index_bundles(const zc_chunk_index* idx, uint64_t* payload_size, ui
 int zc_chunk_index_lookup(zc_ctx* ctx, const zc_chunk_index* idx, const uint8_t* ids, size_t n, uint32_t* bundle,
                           uint64_t* off, uint32_t* size);
 int zc_chunk_index_destroy(zc_chunk_index* idx);
-/* Resolve: ins is the array zc_parse_instructions produced (host; the parse stays on the host, a
- * serial frame walk), instr_bytes the stream's length.  Entry e of kind CHUNK gets (bundle, off,
+/* Resolve: ins is the array zc_parse_instructions produced (host; zc_restore_resolve_device below
+ * takes the entries of a stream parsed in HBM), instr_bytes the stream's length.  Entry e of kind CHUNK gets (bundle, off,
  * size) by lookup; an entry of kind BYTES refers to the instruction stream itself at data_off.
  * Used bundles are the distinct bundles of CHUNK entries in ascending bundle number; slot k is the
  * k-th used bundle and slot n_used the instruction stream (zc_range_index_create's convention).
@@ -878,6 +881,62 @@ int zc_restore_plan_destroy(zc_restore_plan* plan);
  * run an insert or lookup walked. */
 int zc_resolve_last_stats(const zc_ctx* ctx, double* build_ms, double* resolve_ms, uint64_t* table_slots,
                           uint32_t* max_probe);
+
+/* ---- Restore iterations: the instruction stream parsed, resolved and replayed in HBM ----
+ * zbackup stores a backup's instruction stream as a backup of itself (backupFromFileHandle,
+ * zutils.cc:137-166) and restoreIterations (backup_restorer.cc:109-136) undoes that: the restored
+ * bytes of iteration k are the instruction stream of iteration k - 1.  Here those bytes land in HBM,
+ * and these calls keep them there: the parse, the resolve and the replay take and leave their
+ * per-entry data on the device.  What comes to the host is the list of used bundles with their
+ * sizes (the caller fetches those files) and a handful of counters.  Callers detect these entry
+ * points by their symbols (the ABI version stays 5).
+ *
+ * zc_parse_instructions_device is zc_parse_instructions for a stream in device memory: the same
+ * entries in the same order (kind, id, data_off, size) in a zc_instr_set, or ZC_ERR_ARG with *out
+ * NULL and zc_last_error "zc_parse_instructions_device: <what> at byte <N>", <what> and <N> the
+ * host parser's for its first error.  The frame walk is not made message by message (zc_instr_core.h
+ * has the steps); only true message starts are parsed, so whatever a bytes_to_emit payload spells
+ * -- a whole instruction stream, in an iteration -- adds no entry and raises no error.  The call
+ * runs on the context's stream after the work queued on the default stream so far and is complete
+ * on return.  ZC_ERR_ARG before any device work: a NULL pointer with n > 0 (a NULL or zero-length
+ * stream is legal and gives zero entries), a NULL out, 2^32 - 1 bytes or more.
+ * ZC_TEST_INSTR_TILE=<positions> in the environment, a power of two from 64 up to the default,
+ * shrinks the tile, read per call as ZC_TEST_RESOLVE_BITS is: tests only. */
+typedef struct zc_instr_set zc_instr_set; /* n entries x zc_instruction, in HBM */
+int zc_parse_instructions_device(zc_ctx* ctx, const void* d_data, uint64_t n, zc_instr_set** out);
+/* a NULL pointer skips that count; bytes_total: the sum of the BYTES entries' sizes */
+int zc_instr_set_counts(const zc_instr_set* set, uint64_t* n_entries, uint64_t* n_messages, uint64_t* bytes_total);
+/* entries [first, first + count) to a host array: for tests and for naming one entry in an error */
+int zc_instr_set_fetch(const zc_instr_set* set, uint64_t first, uint64_t count, zc_instruction* out);
+int zc_instr_set_destroy(zc_instr_set* set);
+/* The last parse's device times by step (the hop of a position is computed inside the exit
+ * kernel, so hop_ms is 0 and exit_ms holds both; emit_ms: count, scan and write), its tiles and
+ * the steps of the chain walk. */
+int zc_instr_last_stats(const zc_ctx* ctx, double* hop_ms, double* exit_ms, double* chain_ms, double* emit_ms,
+                        uint64_t* tiles, uint64_t* chain_hops);
+/* zc_restore_resolve from a zc_instr_set: the same kernels, nothing per entry uploaded, and the
+ * plan keeps slot, off, size and dst in HBM; used, used_size and the counters come to the host.
+ * zc_restore_plan_counts answers as before; zc_restore_plan_fetch downloads such a plan's lists on
+ * demand; zc_restore_plan_entry gives one entry of either kind of plan (a NULL pointer skips that
+ * field), to name first_missing or first_dup.  The parser has checked what zc_restore_resolve
+ * checks of its array (kinds, BYTES bounds and sum). */
+int zc_restore_resolve_device(zc_ctx* ctx, const zc_chunk_index* idx, const zc_instr_set* set,
+                              zc_restore_plan** plan);
+int zc_restore_plan_entry(const zc_restore_plan* plan, uint64_t e, uint32_t* slot, uint64_t* off, uint64_t* size,
+                          uint64_t* dst);
+/* used and used_size alone (n_used each; a NULL pointer skips that array): what a caller needs to
+ * fetch the bundles, from host memory whichever way the plan was made */
+int zc_restore_plan_used(const zc_restore_plan* plan, uint32_t* used, uint64_t* used_size);
+/* The plan's copies, HBM to HBM: entry e's size bytes from slot_base[slot[e]] + off[e] to
+ * d_out + dst[e].  slot_base is a host array of n_used + 1 device pointers: slot k the decoded
+ * payload of used[k], slot n_used the instruction stream the plan was parsed from.  A plan made
+ * by zc_restore_resolve works too: its lists are uploaded on its first replay and kept.  An entry
+ * longer than 64 KiB is split over waves.  Runs on the context's stream after the work queued on
+ * the default stream so far; complete on return.  ZC_ERR_ARG with a message, before any device
+ * work: n_slots != n_used + 1, a NULL base for a slot the plan uses, length > out_cap, a plan with
+ * missing ids or duplicate-flagged used bundles. */
+int zc_restore_replay(zc_ctx* ctx, const zc_restore_plan* plan, const void* const* slot_base, size_t n_slots,
+                      void* d_out, uint64_t out_cap);
 
 /* ---- LZMA bundles: xz streams decoded on the device ----
  * zbackup's default compression method: Bundle::Creator writes a bundle's payload through

@@ -1512,6 +1512,154 @@ public:
       throw exDuplicateChunks( "bundle " + hex( (uint8_t const *)bundleIds[ out.used[ out.slot[ firstDup ] ] ].data(), 24 ) +
                                " holds a chunk id twice" );
   }
+
+  friend class GpuBackupRestorer;
+};
+
+/// restoreIterations (backup_restorer.cc:109-136) with every intermediate
+/// instruction stream kept in HBM: backup_data is uploaded once, then
+/// iterations + 1 rounds of zc_parse_instructions_device,
+/// zc_restore_resolve_device and zc_restore_replay, each round's output the next
+/// round's stream.  Per round the host sees the used bundles and their payload
+/// sizes, fetches those payloads from the PayloadSource (each bundle once: a
+/// payload stays in HBM for the rounds that follow) and nothing per entry.  The
+/// user data comes back in one read at the end.  Throws
+/// GpuResidentChunkIndex::exNoSuchChunk and exDuplicateChunks, as
+/// GpuResidentChunkIndex::plan does.  Uses the C ABI only.
+class GpuBackupRestorer: NoCopy
+{
+public:
+  typedef GpuIndexedRestorer::PayloadSource PayloadSource;  // getPayload( the index's bundle number, payload )
+
+private:
+  // device buffers of one call, freed with it
+  struct Buffers: NoCopy
+  {
+    zc_ctx * ctx;
+    std::vector< void * > all;
+    explicit Buffers( zc_ctx * c ): ctx( c ) {}
+    void * get( uint64_t bytes )
+    {
+      void * p = 0;
+      zcCheck( zc_device_alloc( ctx, bytes, &p ), ctx, "zc_device_alloc" );
+      all.push_back( p );
+      return p;
+    }
+    void drop( void * p )
+    {
+      for ( size_t i = 0; i < all.size(); ++i )
+        if ( all[ i ] == p )
+        {
+          zc_device_free( ctx, p );
+          all.erase( all.begin() + i );
+          return;
+        }
+    }
+    ~Buffers()
+    {
+      for ( size_t i = 0; i < all.size(); ++i )
+        zc_device_free( ctx, all[ i ] );
+    }
+  };
+
+  struct Handles: NoCopy
+  {
+    zc_instr_set * set;
+    zc_restore_plan * plan;
+    Handles(): set( 0 ), plan( 0 ) {}
+    ~Handles()
+    {
+      if ( plan )
+        zc_restore_plan_destroy( plan );
+      if ( set )
+        zc_instr_set_destroy( set );
+    }
+  };
+
+public:
+  /// BackupInfoT: zbackup's BackupInfo, or anything with backup_data() and
+  /// iterations().  out: the user data.  roundsOut, if given: the length of
+  /// every round's output, the user data's last.
+  template< class BackupInfoT >
+  static void restoreIterations( BackupInfoT const & info, GpuResidentChunkIndex & index, PayloadSource & source,
+                                 string & out, std::vector< uint64_t > * roundsOut = 0 )
+  {
+    zc_ctx * ctx = index.ctx;
+    Buffers bufs( ctx );
+    string const & backupData = info.backup_data();
+    void * stream = bufs.get( backupData.size() );
+    uint64_t n = backupData.size();
+    zcCheck( zc_upload( ctx, stream, backupData.data(), n ), ctx, "zc_upload" );
+    std::vector< void * > resident( index.bundles(), (void *) 0 );  // bundle -> its payload in HBM
+    for ( uint64_t round = 0; round <= (uint64_t) info.iterations(); ++round )
+    {
+      Handles h;
+      zcCheck( zc_parse_instructions_device( ctx, n ? stream : 0, n, &h.set ), ctx, "zc_parse_instructions_device" );
+      zcCheck( zc_restore_resolve_device( ctx, index.index, h.set, &h.plan ), ctx, "zc_restore_resolve_device" );
+      uint64_t entries = 0, used = 0, length = 0, missing = 0, firstMissing = 0, dupUsed = 0, firstDup = 0;
+      zc_restore_plan_counts( h.plan, &entries, &used, &length, &missing, &firstMissing, &dupUsed, &firstDup );
+      std::vector< uint32_t > usedBundle( used + 1 );
+      std::vector< uint64_t > usedSize( used + 1 );
+      zc_restore_plan_used( h.plan, usedBundle.data(), usedSize.data() );
+      if ( missing )
+      {
+        zc_instruction one;  // the one entry the message names
+        if ( zc_instr_set_fetch( h.set, firstMissing, 1, &one ) != ZC_OK )
+          throw std::runtime_error( string( "zc_instr_set_fetch: " ) + zc_last_error( 0 ) );
+        throw GpuResidentChunkIndex::exNoSuchChunk( "chunk " + GpuResidentChunkIndex::hex( one.id, 24 ) +
+                                                    " is in no bundle of the index" );
+      }
+      if ( dupUsed )
+      {
+        uint32_t slot = 0;
+        if ( zc_restore_plan_entry( h.plan, firstDup, &slot, 0, 0, 0 ) != ZC_OK )
+          throw std::runtime_error( string( "zc_restore_plan_entry: " ) + zc_last_error( 0 ) );
+        throw GpuResidentChunkIndex::exDuplicateChunks(
+          "bundle " + GpuResidentChunkIndex::hex( (uint8_t const *) index.bundleIds[ usedBundle[ slot ] ].data(), 24 ) +
+          " holds a chunk id twice" );
+      }
+      std::vector< void const * > slots( used + 1 );
+      for ( uint64_t k = 0; k < used; ++k )
+      {
+        uint32_t b = usedBundle[ k ];
+        if ( !resident[ b ] )
+        {
+          string payload;
+          source.getPayload( b, payload );
+          if ( payload.size() != usedSize[ k ] )
+            throw std::runtime_error( "GpuBackupRestorer: a payload's size differs from the index's" );
+          void * p = bufs.get( payload.size() );
+          zcCheck( zc_upload( ctx, p, payload.data(), payload.size() ), ctx, "zc_upload" );
+          resident[ b ] = p;
+        }
+        slots[ k ] = resident[ b ];
+      }
+      slots[ used ] = stream;  // the round's bytes_to_emit runs are read from its own stream
+      void * next = bufs.get( length );
+      zcCheck( zc_restore_replay( ctx, h.plan, slots.data(), slots.size(), next, length ), ctx, "zc_restore_replay" );
+      bufs.drop( stream );  // the replay is complete: nothing reads the round's stream any more
+      stream = next;
+      n = length;
+      if ( roundsOut )
+        roundsOut->push_back( length );
+    }
+    // the user data, one read through the range reader's staging buffer
+    out.resize( n );
+    if ( n )
+    {
+      zc_range_index * one = 0;
+      uint32_t slot = 0;
+      uint64_t zero = 0;
+      zcCheck( zc_range_index_create( ctx, &n, 1, &slot, &zero, &n, 1, &one ), ctx, "zc_range_index_create" );
+      int rc = zc_range_set_slot( one, 0, stream );
+      if ( rc == ZC_OK )
+        rc = zc_range_read_host( ctx, one, &zero, &n, 1, &out[ 0 ], &zero );
+      string err = rc == ZC_OK ? string() : string( zc_last_error( ctx ) );
+      zc_range_index_destroy( one );
+      if ( rc != ZC_OK )
+        throw std::runtime_error( "GpuBackupRestorer: reading the restored data: " + err );
+    }
+  }
 };
 
 #endif

@@ -8,7 +8,8 @@ from ._lib import ZC_BYTES, ZC_CHUNK_DUP, ZC_CHUNK_NEW, ZcError, load  # noqa: F
 from .chunker import (META_DTYPE, RECORD_DTYPE, BackupCreator, Sha256, anchor_def, chunk_id_blob,  # noqa: F401
                       fill_splitmix64, serialize_instruction)
 from .bundle import BundleCompressor, BundleDecompressor, bundle_file_size, parse_backup_data  # noqa: F401
-from .restore import IndexedRestorer, RangeIndex, Restorer  # noqa: F401
+from .restore import (DevicePlan, IndexedRestorer, InstructionSet, RangeIndex, Restorer,  # noqa: F401
+                      XzBodiesPayloads)
 from .collect import Collector, GcPlan  # noqa: F401
 from .adopt import Adopter, AdoptReport, read_sidecar, write_sidecar  # noqa: F401
 from .index import (BundleInfos, ChunkIndex, IndexLoader, IndexSet, ResidentIndexSet, ResolvedStream,  # noqa: F401

@@ -37,7 +37,10 @@ EXPORTS = ["zc_create", "zc_destroy", "zc_seed_index", "zc_get_input_buffer",
            "zc_xz_capacity", "zc_xz_encode", "zc_xz_encode_host", "zc_xz_encode_last_stats", "zc_xz_encode_last_schedule",
            "zc_chunk_index_create", "zc_chunk_index_create_arrays", "zc_chunk_index_counts", "zc_chunk_index_bundles",
            "zc_chunk_index_lookup", "zc_chunk_index_destroy", "zc_restore_resolve", "zc_restore_plan_counts",
-           "zc_restore_plan_fetch", "zc_restore_plan_destroy", "zc_resolve_last_stats"]
+           "zc_restore_plan_fetch", "zc_restore_plan_destroy", "zc_resolve_last_stats",
+           "zc_parse_instructions_device", "zc_instr_set_counts", "zc_instr_set_fetch", "zc_instr_set_destroy",
+           "zc_instr_last_stats", "zc_restore_resolve_device", "zc_restore_plan_entry", "zc_restore_plan_used",
+           "zc_restore_replay"]
 (ZC_INDEX_OK, ZC_INDEX_BAD_SIZE, ZC_INDEX_BAD_PADDING, ZC_INDEX_TRUNCATED, ZC_INDEX_BAD_VERSION, ZC_INDEX_BAD_MESSAGE,
  ZC_INDEX_BAD_BUNDLE_ID, ZC_INDEX_BAD_CHUNK_ID, ZC_INDEX_BAD_ADLER) = range(9)
 INDEX_STATUS_NAMES = {0: "ok", 1: "bad file size", 2: "bad padding", 3: "truncated", 4: "unsupported version",
@@ -302,6 +305,17 @@ def load(path=LIB_PATH):
         "zc_restore_plan_destroy": (i32, [vp]),
         "zc_resolve_last_stats": (i32, [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
                                         ctypes.POINTER(u64), ctypes.POINTER(u32)]),
+        # restore iterations: (ctx, d_data, n, &set); (set, first, count, out)
+        "zc_parse_instructions_device": (i32, [vp, vp, u64, ctypes.POINTER(vp)]),
+        "zc_instr_set_counts": (i32, [vp] + [ctypes.POINTER(u64)] * 3),
+        "zc_instr_set_fetch": (i32, [vp, u64, u64, vp]),
+        "zc_instr_set_destroy": (i32, [vp]),
+        "zc_instr_last_stats": (i32, [vp] + [ctypes.POINTER(ctypes.c_double)] * 4 + [ctypes.POINTER(u64)] * 2),
+        # (ctx, idx, set, &plan); (plan, e, &slot, &off, &size, &dst); (ctx, plan, slot_base, n_slots, d_out, out_cap)
+        "zc_restore_resolve_device": (i32, [vp, vp, vp, ctypes.POINTER(vp)]),
+        "zc_restore_plan_entry": (i32, [vp, u64, ctypes.POINTER(u32)] + [ctypes.POINTER(u64)] * 3),
+        "zc_restore_plan_used": (i32, [vp, vp, vp]),
+        "zc_restore_replay": (i32, [vp, vp, vp, sz, vp, u64]),
         "zc_device_alloc": (i32, [vp, u64, ctypes.POINTER(vp)]),
         "zc_device_free": (i32, [vp, vp]),
         "zc_upload": (i32, [vp, vp, vp, u64]),

@@ -655,6 +655,8 @@ struct ResolveTimes {
   double build_ms, resolve_ms;  // the last build's kernels; the last resolve's or lookup's
   uint64_t table_slots;         // of the index the last call built or read
   uint32_t max_probe;           // the longest probe run of the last call
+  double replay_ms;             // the last replay's kernels
+  uint64_t replay_pieces;       // and its copies
 };
 ResolveScratch* resolve_scratch_new();
 void resolve_scratch_free(ResolveScratch* s);
@@ -677,13 +679,47 @@ int chunk_index_lookup(ResolveScratch* s, const zc_chunk_index* ix, const uint8_
 // *bytes_total: the sum of the BYTES entries' sizes, which restore_resolve takes
 int resolve_validate(const zc_instruction* ins, uint64_t n, uint64_t instr_bytes, zc_restore_plan* const* out,
                      uint64_t* bytes_total, std::string& err);
-int restore_resolve(ResolveScratch* s, const zc_chunk_index* ix, const zc_instruction* ins, uint64_t n,
-                    uint64_t bytes_total, zc_restore_plan** out, hipStream_t st, std::string& err);
+// d_ins: a zc_instr_set's entries in HBM (ins NULL): the plan keeps its per-entry lists on the device
+int restore_resolve(ResolveScratch* s, const zc_chunk_index* ix, const zc_instruction* ins, const uint32_t* d_ins,
+                    uint64_t n, uint64_t bytes_total, zc_restore_plan** out, hipStream_t st, std::string& err);
+int resolve_device_validate(const zc_instr_set* set, int index_device, zc_restore_plan* const* out,
+                            const uint32_t** d_ins, uint64_t* n, uint64_t* bytes_total, std::string& err);
 void restore_plan_counts(const zc_restore_plan* pl, uint64_t* n_entries, uint64_t* n_used, uint64_t* length,
                          uint64_t* n_missing, uint64_t* first_missing, uint64_t* n_dup_used, uint64_t* first_dup);
-void restore_plan_fetch(const zc_restore_plan* pl, uint32_t* used, uint64_t* used_size, uint32_t* slot, uint64_t* off,
-                        uint64_t* size, uint64_t* dst);
+int restore_plan_fetch(const zc_restore_plan* pl, uint32_t* used, uint64_t* used_size, uint32_t* slot, uint64_t* off,
+                       uint64_t* size, uint64_t* dst, std::string& err);
+void restore_plan_used(const zc_restore_plan* pl, uint32_t* used, uint64_t* used_size);
+int restore_plan_entry(const zc_restore_plan* pl, uint64_t e, uint32_t* slot, uint64_t* off, uint64_t* size,
+                       uint64_t* dst, std::string& err);
 void restore_plan_destroy(zc_restore_plan* pl);
+// replay_validate checks what the host can see (no device work; ctx_device -1:
+// there is no context yet); ev_in orders the context stream after the legacy default stream
+int replay_validate(const zc_restore_plan* pl, int ctx_device, const void* const* slot_base, size_t n_slots,
+                    const void* d_out, uint64_t out_cap, std::string& err);
+int restore_replay(ResolveScratch* s, const zc_restore_plan* pl, const void* const* slot_base, size_t n_slots,
+                   void* d_out, hipEvent_t ev_in, hipStream_t st, std::string& err);
+
+// zc_instr.hip: a BackupInstruction stream in HBM to zc_instruction entries in
+// HBM (zc_instr_core.h).  instr_validate checks what the host can see (no
+// device, no context); each call returns a zc_status with its message in `err`.
+struct InstrScratch;
+struct InstrTimes {
+  double hop_ms, exit_ms, chain_ms, emit_ms;  // hop runs inside the exit kernel: hop_ms is 0
+  uint64_t tiles, chain_hops;
+};
+InstrScratch* instr_scratch_new();
+void instr_scratch_free(InstrScratch* s);
+const InstrTimes* instr_times(const InstrScratch* s);
+int instr_validate(const void* d_data, uint64_t n, zc_instr_set* const* out, std::string& err);
+// ev_in orders the context stream after the legacy default stream
+int instr_parse(InstrScratch* s, int device, const void* d_data, uint64_t n, zc_instr_set** out, hipEvent_t ev_in,
+                hipStream_t st, std::string& err);
+void instr_set_counts(const zc_instr_set* set, uint64_t* n_entries, uint64_t* n_messages, uint64_t* bytes_total);
+// the set's device, entries (twelve 32-bit words each) and counts, for zc_resolve.hip
+void instr_set_view(const zc_instr_set* set, int* device, const uint32_t** d_ins, uint64_t* n_entries,
+                    uint64_t* bytes_total);
+int instr_set_fetch(const zc_instr_set* set, uint64_t first, uint64_t count, zc_instruction* out, std::string& err);
+void instr_set_destroy(zc_instr_set* set);
 
 // zc_xz.hip: LZMA bundles, xz streams decoded to their payloads (zc_xz_core.h).
 // xz_validate checks what the host can see (no device, no context); xz_decode

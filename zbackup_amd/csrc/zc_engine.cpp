@@ -544,6 +544,7 @@ struct zc_ctx {
   RangeScratch* range = nullptr;  // random-access restore's buffers (zc_range.hip), made on first use
   IndexScratch* index = nullptr;  // index files' buffers (zc_index.hip), made on first use
   ResolveScratch* rs = nullptr;   // the chunk index's build and resolve buffers (zc_resolve.hip), made on first use
+  InstrScratch* instr = nullptr;  // the device parse's exits and tile tables (zc_instr.hip), made on first use
   XzScratch* xz = nullptr;        // LZMA bundles' buffers (zc_xz.hip), made on first use
   XzEncScratch* xzenc = nullptr;  // the encoder's tables and candidates (zc_xzenc.hip), made on first use
 
@@ -3392,6 +3393,7 @@ int zc_destroy(zc_ctx* c) {
     range_scratch_free(c->range);
     index_scratch_free(c->index);
     resolve_scratch_free(c->rs);
+    if (c->instr) instr_scratch_free(c->instr);
     xz_scratch_free(c->xz);
     xzenc_scratch_free(c->xzenc);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -4853,8 +4855,100 @@ int zc_restore_resolve(zc_ctx* c, const zc_chunk_index* idx, const zc_instructio
     }
   }
   return resolve_entry(c, "zc_restore_resolve", checked, err, [&](std::string& e) {
-    return restore_resolve(c->rs, idx, ins, n, bytes_total, plan, c->stream, e);
+    return restore_resolve(c->rs, idx, ins, nullptr, n, bytes_total, plan, c->stream, e);
   });
+}
+
+int zc_restore_resolve_device(zc_ctx* c, const zc_chunk_index* idx, const zc_instr_set* set, zc_restore_plan** plan) {
+  ZC_LOCK(c);
+  std::string err;
+  int checked = ZC_OK;
+  const uint32_t* d_ins = nullptr;
+  uint64_t n = 0, bytes_total = 0;
+  if (!idx) {
+    err = "null index";
+    checked = ZC_ERR_ARG;
+  } else {
+    checked = resolve_device_validate(set, chunk_index_device(idx), plan, &d_ins, &n, &bytes_total, err);
+    if (checked == ZC_OK && c && chunk_index_device(idx) != c->device) {
+      err = "the index lives on another device than the context";
+      checked = ZC_ERR_ARG;
+    }
+  }
+  return resolve_entry(c, "zc_restore_resolve_device", checked, err, [&](std::string& e) {
+    // a set of no entries has no device array: the host path's empty plan
+    return restore_resolve(c->rs, idx, nullptr, n ? d_ins : nullptr, n, bytes_total, plan, c->stream, e);
+  });
+}
+
+int zc_restore_replay(zc_ctx* c, const zc_restore_plan* plan, const void* const* slot_base, size_t n_slots,
+                      void* d_out, uint64_t out_cap) {
+  ZC_LOCK(c);
+  std::string err;
+  const int checked = replay_validate(plan, c ? c->device : -1, slot_base, n_slots, d_out, out_cap, err);
+  return resolve_entry(c, "zc_restore_replay", checked, err, [&](std::string& e) {
+    return restore_replay(c->rs, plan, slot_base, n_slots, d_out, c->ev_in, c->stream, e);
+  });
+}
+
+// ---- the instruction stream parsed in HBM (zc_instr.hip) ----
+
+int zc_parse_instructions_device(zc_ctx* c, const void* d_data, uint64_t n, zc_instr_set** out) {
+  ZC_LOCK(c);
+  std::string err;
+  if (out) *out = nullptr;
+  const int checked = instr_validate(d_data, n, out, err);
+  if (checked != ZC_OK) return ctx_arg_error(c, ("zc_parse_instructions_device: " + err).c_str());
+  if (!c) return ctx_arg_error(c, "zc_parse_instructions_device: null context");
+  int rc;
+  try {
+    DeviceGuard g(c->device);
+    if (!c->instr) c->instr = instr_scratch_new();
+    rc = instr_parse(c->instr, c->device, d_data, n, out, c->ev_in, c->stream, err);
+  } catch (const ZcError& e) {
+    return fail(c, e);
+  } catch (const std::bad_alloc&) {
+    return fail(c, ZcError{ZC_ERR_NOMEM, "host allocation failed"});
+  }
+  if (rc != ZC_OK)
+    c->err = "zc_parse_instructions_device: " + err;
+  else
+    c->err.clear();
+  return rc;
+}
+
+int zc_instr_set_counts(const zc_instr_set* set, uint64_t* n_entries, uint64_t* n_messages, uint64_t* bytes_total) {
+  if (!set) return host_arg_error("zc_instr_set_counts: null set");
+  instr_set_counts(set, n_entries, n_messages, bytes_total);
+  return ZC_OK;
+}
+
+int zc_instr_set_fetch(const zc_instr_set* set, uint64_t first, uint64_t count, zc_instruction* out) {
+  if (!set) return host_arg_error("zc_instr_set_fetch: null set");
+  std::string err;
+  const int rc = instr_set_fetch(set, first, count, out, err);
+  g_host_err = rc != ZC_OK ? "zc_instr_set_fetch: " + err : std::string();
+  return rc;
+}
+
+int zc_instr_set_destroy(zc_instr_set* set) {
+  if (!set) return host_arg_error("zc_instr_set_destroy: null set");
+  instr_set_destroy(set);
+  return ZC_OK;
+}
+
+int zc_instr_last_stats(const zc_ctx* c, double* hop_ms, double* exit_ms, double* chain_ms, double* emit_ms,
+                        uint64_t* tiles, uint64_t* chain_hops) {
+  ZC_LOCK(c);
+  if (!c) return host_arg_error("zc_instr_last_stats: null context");
+  const InstrTimes t = c->instr ? *instr_times(c->instr) : InstrTimes{};
+  if (hop_ms) *hop_ms = t.hop_ms;
+  if (exit_ms) *exit_ms = t.exit_ms;
+  if (chain_ms) *chain_ms = t.chain_ms;
+  if (emit_ms) *emit_ms = t.emit_ms;
+  if (tiles) *tiles = t.tiles;
+  if (chain_hops) *chain_hops = t.chain_hops;
+  return ZC_OK;
 }
 
 int zc_restore_plan_counts(const zc_restore_plan* plan, uint64_t* n_entries, uint64_t* n_used, uint64_t* length,
@@ -4867,8 +4961,26 @@ int zc_restore_plan_counts(const zc_restore_plan* plan, uint64_t* n_entries, uin
 int zc_restore_plan_fetch(const zc_restore_plan* plan, uint32_t* used, uint64_t* used_size, uint32_t* slot,
                           uint64_t* off, uint64_t* size, uint64_t* dst) {
   if (!plan) return host_arg_error("zc_restore_plan_fetch: null plan");
-  restore_plan_fetch(plan, used, used_size, slot, off, size, dst);
+  std::string err;
+  const int rc = restore_plan_fetch(plan, used, used_size, slot, off, size, dst, err);
+  g_host_err = rc != ZC_OK ? "zc_restore_plan_fetch: " + err : std::string();
+  return rc;
+}
+
+int zc_restore_plan_used(const zc_restore_plan* plan, uint32_t* used, uint64_t* used_size) {
+  if (!plan) return host_arg_error("zc_restore_plan_used: null plan");
+  restore_plan_used(plan, used, used_size);
+  g_host_err.clear();
   return ZC_OK;
+}
+
+int zc_restore_plan_entry(const zc_restore_plan* plan, uint64_t e, uint32_t* slot, uint64_t* off, uint64_t* size,
+                          uint64_t* dst) {
+  if (!plan) return host_arg_error("zc_restore_plan_entry: null plan");
+  std::string err;
+  const int rc = restore_plan_entry(plan, e, slot, off, size, dst, err);
+  g_host_err = rc != ZC_OK ? "zc_restore_plan_entry: " + err : std::string();
+  return rc;
 }
 
 int zc_restore_plan_destroy(zc_restore_plan* plan) {

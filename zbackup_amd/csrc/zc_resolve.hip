@@ -26,6 +26,9 @@
 //             entry sizes (dst)
 //             zc_rs_used          the used bundles, ascending, with their payload sizes
 //             zc_rs_slots         per entry: its slot
+//   replay    zc_rp_pieces        per entry: its copies of at most 64 KiB (zclzo::kPiece), scanned
+//             zc_rp_copy          a wave per piece: the entry by binary search over the scan, then
+//                                 zccopy::wave_copy from the entry's slot to the output
 //
 // The outputs are functions of the final tables, which do not depend on the
 // order of the inserts (zc_gc_core.h, zc_resolve_core.h); only max_probe (a
@@ -41,12 +44,15 @@
 
 #include <algorithm>
 #include <chrono>
+#include <mutex>
 #include <string>
 #include <vector>
 
 #include "../../include/zchunk.h"
 #define ZC_HD __host__ __device__
+#include "zc_copy_body.h"
 #include "zc_device.h"
+#include "zc_lzo_core.h"
 #include "zc_resolve_core.h"
 
 static_assert(sizeof(zc_instruction) == 48, "zc_instruction is read as twelve 32-bit words");
@@ -320,6 +326,42 @@ __global__ __launch_bounds__(kBlock) void zc_rs_slots(const uint32_t* __restrict
   }
 }
 
+constexpr uint64_t kPiece = zclzo::kPiece;  // the scatter's piece: a long entry is split over waves
+
+__global__ __launch_bounds__(kBlock) void zc_rp_pieces(const uint64_t* __restrict__ esize, uint64_t n,
+                                                       uint64_t* __restrict__ pc) {
+  const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+  for (uint64_t e = (uint64_t)blockIdx.x * kBlock + threadIdx.x; e < n; e += stride)
+    pc[e] = esize[e] / kPiece + (esize[e] % kPiece != 0);
+}
+
+// pstart: the exclusive scan of the piece counts, pstart[n] = pieces.  base: n_base device pointers.
+__global__ __launch_bounds__(kBlock) void zc_rp_copy(const uint64_t* __restrict__ pstart, uint64_t n, uint64_t pieces,
+                                                     const uint32_t* __restrict__ slot,
+                                                     const uint64_t* __restrict__ eoff,
+                                                     const uint64_t* __restrict__ esize,
+                                                     const uint64_t* __restrict__ dst,
+                                                     const uint8_t* const* __restrict__ base, uint32_t n_base,
+                                                     uint8_t* __restrict__ out) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t waves = (uint64_t)gridDim.x * (kBlock / 64);
+  for (uint64_t q = (uint64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6); q < pieces; q += waves) {
+    // the entry of piece q: pstart[lo] <= q < pstart[hi]; bound: 32 halvings, n < 2^32
+    uint64_t lo = 0, hi = n;
+    while (hi - lo > 1) {
+      const uint64_t mid = lo + (hi - lo) / 2;
+      if (pstart[mid] <= q)
+        lo = mid;
+      else
+        hi = mid;
+    }
+    const uint64_t at = (q - pstart[lo]) * kPiece, size = esize[lo];
+    const uint32_t k = slot[lo];
+    if (k >= n_base || at >= size) continue;  // neither happens on a plan restore_replay_validate let through
+    zccopy::wave_copy(out + dst[lo] + at, base[k] + eoff[lo] + at, min(kPiece, size - at), lane);
+  }
+}
+
 template <class T>
 struct Buf {
   T* p = nullptr;
@@ -382,17 +424,25 @@ struct zc_chunk_index {
   zc::Buf<uint8_t> bdup;
 };
 
-// a resolved backup, on the host
+// a resolved backup: the counters and the used bundles on the host; the per-entry lists on the host
+// (zc_restore_resolve) or in HBM (zc_restore_resolve_device, and a host plan's copy for its replays)
 struct zc_restore_plan {
   uint64_t n_entries = 0, n_used = 0, length = 0, n_missing = 0, first_missing = 0, n_dup_used = 0, first_dup = 0;
+  uint64_t bytes_total = 0;  // the BYTES entries' sizes: above 0, a replay reads the instruction stream's slot
   std::vector<uint32_t> used, slot;
   std::vector<uint64_t> used_size, off, size, dst;
+  bool on_device = false;  // the host vectors of the per-entry lists are empty
+  int device = 0;
+  mutable std::mutex mu;          // guards a host plan's one upload
+  mutable bool resident = false;  // d_* hold the lists
+  mutable zc::Buf<uint32_t> d_slot;
+  mutable zc::Buf<uint64_t> d_off, d_size, d_dst;
 };
 
 namespace zc {
 
 struct ResolveScratch {
-  Buf<uint64_t> ids, bf, run, tsum, keys, off64, eoff, esize, dst, slotof, used_size;
+  Buf<uint64_t> ids, bf, run, tsum, keys, off64, eoff, esize, dst, slotof, used_size, pc, pstart, base;
   Buf<uint32_t> sizes, pairs, ins, bundle32, size32, ebund, slot, used;
   Buf<uint8_t> bused;
   Buf<RsDev> dev;
@@ -669,8 +719,20 @@ int resolve_validate(const zc_instruction* ins, uint64_t n, uint64_t instr_bytes
   return ZC_OK;
 }
 
-int restore_resolve(ResolveScratch* s, const zc_chunk_index* ix, const zc_instruction* ins, uint64_t n,
-                    uint64_t bytes_total, zc_restore_plan** out, hipStream_t st, std::string& err) {
+int resolve_device_validate(const zc_instr_set* set, int index_device, zc_restore_plan* const* out, const uint32_t** d_ins,
+                            uint64_t* n, uint64_t* bytes_total, std::string& err) {
+  if (!out) return arg_error(err, "null plan pointer");
+  if (!set) return arg_error(err, "null instruction set");
+  int device = 0;
+  instr_set_view(set, &device, d_ins, n, bytes_total);
+  if (device != index_device) return arg_error(err, "the instruction set lives on another device than the index");
+  return ZC_OK;
+}
+
+// d_ins: a zc_instr_set's entries in HBM (ins is NULL then): nothing per entry is
+// uploaded, and the plan keeps its per-entry lists where the kernels wrote them
+int restore_resolve(ResolveScratch* s, const zc_chunk_index* ix, const zc_instruction* ins, const uint32_t* d_ins,
+                    uint64_t n, uint64_t bytes_total, zc_restore_plan** out, hipStream_t st, std::string& err) {
   *out = nullptr;
   int rc = first_use(s, st, err);
   if (rc != ZC_OK) return rc;
@@ -683,14 +745,29 @@ int restore_resolve(ResolveScratch* s, const zc_chunk_index* ix, const zc_instru
     ~Drop() { delete p; }
   } drop{pl};
   pl->n_entries = n;
+  pl->bytes_total = bytes_total;
+  pl->device = ix->device;
+  pl->on_device = d_ins != nullptr;
   if (n) {
     const uint64_t B = ix->n_bundles;
-    RCK(s->ins.ensure(12 * n));
+    uint32_t* d_slot = nullptr;
+    uint64_t *d_off = nullptr, *d_size = nullptr, *d_dst = nullptr;
+    if (d_ins) {
+      RCK(pl->d_slot.ensure(n));
+      RCK(pl->d_off.ensure(n));
+      RCK(pl->d_size.ensure(n));
+      RCK(pl->d_dst.ensure(n));
+      d_slot = pl->d_slot.p, d_off = pl->d_off.p, d_size = pl->d_size.p, d_dst = pl->d_dst.p;
+      pl->resident = true;
+    } else {
+      RCK(s->ins.ensure(12 * n));
+      RCK(s->eoff.ensure(n));
+      RCK(s->esize.ensure(n));
+      RCK(s->dst.ensure(n));
+      RCK(s->slot.ensure(n));
+      d_slot = s->slot.p, d_off = s->eoff.p, d_size = s->esize.p, d_dst = s->dst.p;
+    }
     RCK(s->ebund.ensure(n));
-    RCK(s->eoff.ensure(n));
-    RCK(s->esize.ensure(n));
-    RCK(s->dst.ensure(n));
-    RCK(s->slot.ensure(n));
     RCK(s->bused.ensure(B));
     RCK(s->slotof.ensure(B));
     RCK(s->used.ensure(B));
@@ -698,30 +775,34 @@ int restore_resolve(ResolveScratch* s, const zc_chunk_index* ix, const zc_instru
     RCK(s->tsum.ensure((std::max(n, B) + kTile - 1) / kTile));  // both scans' tiles: no buffer is made mid-stream
     RsDev h = fresh_dev();
     RCK(hipMemcpyAsync(s->dev.p, &h, sizeof h, hipMemcpyHostToDevice, st));
-    RCK(hipMemcpyAsync(s->ins.p, ins, 48 * n, hipMemcpyHostToDevice, st));
+    if (!d_ins) {
+      RCK(hipMemcpyAsync(s->ins.p, ins, 48 * n, hipMemcpyHostToDevice, st));
+      d_ins = s->ins.p;
+    }
     if (B) RCK(hipMemsetAsync(s->bused.p, 0, B, st));
     RCK(hipEventRecord(s->ev[0], st));
     const int gn = grid_for(s, n);
-    zc_rs_probe<<<gn, kBlock, 0, st>>>(view_of(ix), s->ins.p, n, s->ebund.p, s->eoff.p, s->esize.p, s->bused.p,
-                                       s->dev.p);
+    zc_rs_probe<<<gn, kBlock, 0, st>>>(view_of(ix), d_ins, n, s->ebund.p, d_off, d_size, s->bused.p, s->dev.p);
     rc = scan<uint8_t>(s, s->bused.p, B, s->slotof.p, false, &s->dev.p->total[0], st, err);
     if (rc != ZC_OK) return rc;
-    rc = scan<uint64_t>(s, s->esize.p, n, s->dst.p, false, &s->dev.p->total[1], st, err);
+    rc = scan<uint64_t>(s, d_size, n, d_dst, false, &s->dev.p->total[1], st, err);
     if (rc != ZC_OK) return rc;
     if (B)
       zc_rs_used<<<grid_for(s, B), kBlock, 0, st>>>(s->bused.p, s->slotof.p, ix->bsize.p, B, s->used.p,
                                                     s->used_size.p);
-    zc_rs_slots<<<gn, kBlock, 0, st>>>(s->ebund.p, s->slotof.p, n, s->dev.p, s->slot.p);
+    zc_rs_slots<<<gn, kBlock, 0, st>>>(s->ebund.p, s->slotof.p, n, s->dev.p, d_slot);
     RCK(hipGetLastError());
     RCK(hipEventRecord(s->ev[1], st));
-    pl->slot.resize(n);
-    pl->off.resize(n);
-    pl->size.resize(n);
-    pl->dst.resize(n);
-    RCK(hipMemcpyAsync(pl->slot.data(), s->slot.p, 4 * n, hipMemcpyDeviceToHost, st));
-    RCK(hipMemcpyAsync(pl->off.data(), s->eoff.p, 8 * n, hipMemcpyDeviceToHost, st));
-    RCK(hipMemcpyAsync(pl->size.data(), s->esize.p, 8 * n, hipMemcpyDeviceToHost, st));
-    RCK(hipMemcpyAsync(pl->dst.data(), s->dst.p, 8 * n, hipMemcpyDeviceToHost, st));
+    if (!pl->on_device) {
+      pl->slot.resize(n);
+      pl->off.resize(n);
+      pl->size.resize(n);
+      pl->dst.resize(n);
+      RCK(hipMemcpyAsync(pl->slot.data(), d_slot, 4 * n, hipMemcpyDeviceToHost, st));
+      RCK(hipMemcpyAsync(pl->off.data(), d_off, 8 * n, hipMemcpyDeviceToHost, st));
+      RCK(hipMemcpyAsync(pl->size.data(), d_size, 8 * n, hipMemcpyDeviceToHost, st));
+      RCK(hipMemcpyAsync(pl->dst.data(), d_dst, 8 * n, hipMemcpyDeviceToHost, st));
+    }
     RCK(hipMemcpyAsync(&h, s->dev.p, sizeof h, hipMemcpyDeviceToHost, st));
     RCK(hipStreamSynchronize(st));
     float ms = 0;
@@ -767,17 +848,157 @@ void restore_plan_counts(const zc_restore_plan* pl, uint64_t* n_entries, uint64_
   if (first_dup) *first_dup = pl->first_dup;
 }
 
-void restore_plan_fetch(const zc_restore_plan* pl, uint32_t* used, uint64_t* used_size, uint32_t* slot, uint64_t* off,
-                        uint64_t* size, uint64_t* dst) {
-  const size_t n = pl->n_entries, u = pl->n_used;
-  if (used && u) memcpy(used, pl->used.data(), 4 * u);
-  if (used_size && u) memcpy(used_size, pl->used_size.data(), 8 * u);
-  if (slot && n) memcpy(slot, pl->slot.data(), 4 * n);
-  if (off && n) memcpy(off, pl->off.data(), 8 * n);
-  if (size && n) memcpy(size, pl->size.data(), 8 * n);
-  if (dst && n) memcpy(dst, pl->dst.data(), 8 * n);
+namespace {
+
+// count entries from `first` of a device plan's lists to host arrays (NULL skips)
+int plan_download(const zc_restore_plan* pl, uint64_t first, uint64_t count, uint32_t* slot, uint64_t* off,
+                  uint64_t* size, uint64_t* dst, std::string& err) {
+  SetDevice g(pl->device);
+  hipError_t e = hipSuccess;
+  if (slot) e = hipMemcpy(slot, pl->d_slot.p + first, 4 * count, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && off) e = hipMemcpy(off, pl->d_off.p + first, 8 * count, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && size) e = hipMemcpy(size, pl->d_size.p + first, 8 * count, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && dst) e = hipMemcpy(dst, pl->d_dst.p + first, 8 * count, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) {
+    err = hipGetErrorString(e);
+    return ZC_ERR_HIP;
+  }
+  return ZC_OK;
 }
 
-void restore_plan_destroy(zc_restore_plan* pl) { delete pl; }
+}  // namespace
+
+void restore_plan_used(const zc_restore_plan* pl, uint32_t* used, uint64_t* used_size) {
+  const size_t u = pl->n_used;
+  if (used && u) memcpy(used, pl->used.data(), 4 * u);
+  if (used_size && u) memcpy(used_size, pl->used_size.data(), 8 * u);
+}
+
+int restore_plan_fetch(const zc_restore_plan* pl, uint32_t* used, uint64_t* used_size, uint32_t* slot, uint64_t* off,
+                       uint64_t* size, uint64_t* dst, std::string& err) {
+  const size_t n = pl->n_entries;
+  restore_plan_used(pl, used, used_size);
+  if (!n) return ZC_OK;
+  if (pl->on_device) return plan_download(pl, 0, n, slot, off, size, dst, err);  // on demand: the plan keeps no host copy
+  if (slot) memcpy(slot, pl->slot.data(), 4 * n);
+  if (off) memcpy(off, pl->off.data(), 8 * n);
+  if (size) memcpy(size, pl->size.data(), 8 * n);
+  if (dst) memcpy(dst, pl->dst.data(), 8 * n);
+  return ZC_OK;
+}
+
+int restore_plan_entry(const zc_restore_plan* pl, uint64_t e, uint32_t* slot, uint64_t* off, uint64_t* size,
+                       uint64_t* dst, std::string& err) {
+  if (e >= pl->n_entries) {
+    char msg[120];
+    snprintf(msg, sizeof msg, "entry %llu of %llu", (unsigned long long)e, (unsigned long long)pl->n_entries);
+    return arg_error(err, msg);
+  }
+  if (pl->on_device) return plan_download(pl, e, 1, slot, off, size, dst, err);
+  if (slot) *slot = pl->slot[e];
+  if (off) *off = pl->off[e];
+  if (size) *size = pl->size[e];
+  if (dst) *dst = pl->dst[e];
+  return ZC_OK;
+}
+
+void restore_plan_destroy(zc_restore_plan* pl) {
+  SetDevice g(pl->device);
+  delete pl;
+}
+
+int replay_validate(const zc_restore_plan* pl, int ctx_device, const void* const* slot_base, size_t n_slots,
+                    const void* d_out, uint64_t out_cap, std::string& err) {
+  char msg[200];
+  if (!pl) return arg_error(err, "null plan");
+  if (pl->n_missing) {
+    snprintf(msg, sizeof msg, "the plan has %llu entries whose chunk id is missing (the first is entry %llu)",
+             (unsigned long long)pl->n_missing, (unsigned long long)pl->first_missing);
+    return arg_error(err, msg);
+  }
+  if (pl->n_dup_used) {
+    snprintf(msg, sizeof msg, "the plan uses a bundle that holds a chunk id twice (%llu entries, the first is %llu)",
+             (unsigned long long)pl->n_dup_used, (unsigned long long)pl->first_dup);
+    return arg_error(err, msg);
+  }
+  if (n_slots != pl->n_used + 1) {
+    snprintf(msg, sizeof msg, "%llu slots, the plan has %llu used bundles and the instruction stream",
+             (unsigned long long)n_slots, (unsigned long long)pl->n_used);
+    return arg_error(err, msg);
+  }
+  if (!slot_base) return arg_error(err, "null slot array");
+  for (uint64_t k = 0; k < pl->n_used; k++)
+    if (!slot_base[k] && pl->used_size[k]) {
+      snprintf(msg, sizeof msg, "slot %llu (bundle %u) has no payload", (unsigned long long)k, pl->used[k]);
+      return arg_error(err, msg);
+    }
+  if (pl->bytes_total && !slot_base[pl->n_used])
+    return arg_error(err, "the instruction stream's slot is null and the plan has bytes_to_emit runs");
+  if (pl->length > out_cap) {
+    snprintf(msg, sizeof msg, "%llu bytes to restore, room for %llu", (unsigned long long)pl->length,
+             (unsigned long long)out_cap);
+    return arg_error(err, msg);
+  }
+  if (pl->length && !d_out) return arg_error(err, "null output");
+  if (ctx_device >= 0 && pl->n_entries && pl->device != ctx_device)
+    return arg_error(err, "the plan lives on another device than the context");
+  return ZC_OK;
+}
+
+int restore_replay(ResolveScratch* s, const zc_restore_plan* pl, const void* const* slot_base, size_t n_slots,
+                   void* d_out, hipEvent_t ev_in, hipStream_t st, std::string& err) {
+  int rc = first_use(s, st, err);
+  if (rc != ZC_OK) return rc;
+  const uint64_t n = pl->n_entries;
+  if (!n || !pl->length) return ZC_OK;
+  RCK(s->pc.ensure(n));
+  RCK(s->pstart.ensure(n + 1));
+  RCK(s->base.ensure(n_slots));
+  RCK(s->tsum.ensure((n + kTile - 1) / kTile));
+  {
+    std::lock_guard<std::mutex> lock(pl->mu);
+    if (!pl->resident) {  // a host-made plan: its lists go up once and stay
+      RCK(pl->d_slot.ensure(n));
+      RCK(pl->d_off.ensure(n));
+      RCK(pl->d_size.ensure(n));
+      RCK(pl->d_dst.ensure(n));
+      RCK(hipMemcpyAsync(pl->d_slot.p, pl->slot.data(), 4 * n, hipMemcpyHostToDevice, st));
+      RCK(hipMemcpyAsync(pl->d_off.p, pl->off.data(), 8 * n, hipMemcpyHostToDevice, st));
+      RCK(hipMemcpyAsync(pl->d_size.p, pl->size.data(), 8 * n, hipMemcpyHostToDevice, st));
+      RCK(hipMemcpyAsync(pl->d_dst.p, pl->dst.data(), 8 * n, hipMemcpyHostToDevice, st));
+      RCK(hipStreamSynchronize(st));
+      pl->resident = true;
+    }
+  }
+  // after the work queued on the legacy default stream so far (the payloads' decode, the stream's replay)
+  RCK(hipEventRecord(ev_in, nullptr));
+  RCK(hipStreamWaitEvent(st, ev_in, 0));
+  RsDev h = fresh_dev();
+  RCK(hipMemcpyAsync(s->dev.p, &h, sizeof h, hipMemcpyHostToDevice, st));
+  RCK(hipMemcpyAsync(s->base.p, slot_base, 8 * n_slots, hipMemcpyHostToDevice, st));
+  RCK(hipEventRecord(s->ev[0], st));
+  zc_rp_pieces<<<grid_for(s, n), kBlock, 0, st>>>(pl->d_size.p, n, s->pc.p);
+  rc = scan<uint64_t>(s, s->pc.p, n, s->pstart.p, true, &s->dev.p->total[1], st, err);
+  if (rc != ZC_OK) return rc;
+  RCK(hipGetLastError());
+  // the piece count is the one word that comes back: it sizes the copy's grid
+  RCK(hipMemcpyAsync(&h, s->dev.p, sizeof h, hipMemcpyDeviceToHost, st));
+  RCK(hipStreamSynchronize(st));
+  const uint64_t pieces = h.total[1];
+  if (pieces) {
+    const uint64_t blocks = (pieces + kBlock / 64 - 1) / (kBlock / 64);
+    const int grid = (int)std::min<uint64_t>(blocks, (uint64_t)s->cus * 64);
+    zc_rp_copy<<<grid, kBlock, 0, st>>>(s->pstart.p, n, pieces, pl->d_slot.p, pl->d_off.p, pl->d_size.p, pl->d_dst.p,
+                                        (const uint8_t* const*)s->base.p, (uint32_t)n_slots, (uint8_t*)d_out);
+    RCK(hipGetLastError());
+  }
+  RCK(hipEventRecord(s->ev[1], st));
+  RCK(hipStreamSynchronize(st));
+  float ms = 0;
+  RCK(hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
+  s->times.replay_ms = ms;
+  s->times.replay_pieces = pieces;
+  return ZC_OK;
+}
 
 }  // namespace zc

@@ -18,6 +18,14 @@ LZMA bundles, zbackup's default, need no host decoder: `Restorer.replay_bodies`
 takes their xz bodies and decodes them into the scratch buffer on the device
 (zc_xz_decode), as `IndexedRestorer.decode_payload` does for one slot.
 
+  restoreIterations          -> iterations in HBM         backup_restorer.cc:109-136
+
+`Restorer.restore_iterations` keeps every intermediate instruction stream on the
+device: `parse_device` (zc_parse_instructions_device), `plan_device`
+(zc_restore_resolve_device, a `DevicePlan` whose per-entry lists stay in HBM)
+and `replay_device` (zc_restore_replay) per round, each round's output the next
+round's stream; `XzBodiesPayloads` serves the rounds' bundles from xz bodies.
+
   IndexedRestorer::saveData  -> any byte range            backup_restorer.cc:182-316
 
 `IndexedRestorer` serves batches of (offset, size) reads from the payloads that
@@ -200,8 +208,265 @@ class Restorer:
         dec.decode_bodies(bodies, d_work + stage, d_work, plan.pay_off, plan.pay_size)
         return self.replay(plan, d_work, d_out, out_cap)
 
+    # ---- the same with the stream, the entries and the plan in HBM (restoreIterations) ----
+
+    def parse_device(self, d_stream, n):
+        """zc_parse_instructions_device: the stream's n bytes at d_stream
+        (device memory) to an InstructionSet in HBM.  Raises ZcError with the
+        host parser's text on a malformed stream."""
+        L, ctx = self._comp._L, self._comp._ctx
+        handle = ctypes.c_void_p()
+        rc = L.zc_parse_instructions_device(ctx, d_stream if n else None, int(n), ctypes.byref(handle))
+        _range_check(L, ctx, rc, "zc_parse_instructions_device")
+        return InstructionSet(L, handle)
+
+    def plan_device(self, instr_set, chunk_index):
+        """zc_restore_resolve_device: a DevicePlan whose per-entry lists stay
+        in HBM.  Raises what plan_index raises, in the same words, for a
+        missing id (naming it) and for a used bundle that holds an id twice
+        (naming the bundle): one entry is fetched for the name, no more."""
+        L, ctx = self._comp._L, self._comp._ctx
+        handle = ctypes.c_void_p()
+        rc = L.zc_restore_resolve_device(ctx, chunk_index._live(), instr_set._live(), ctypes.byref(handle))
+        _range_check(L, ctx, rc, "zc_restore_resolve_device")
+        plan = DevicePlan(L, handle)
+        try:
+            if plan.n_missing:
+                blob = instr_set.fetch(plan.first_missing, 1)[0]["id"].tobytes()
+                raise _lib.ZcError(f"restore: chunk id {blob.hex()} is in none of the "
+                                   f"{chunk_index.counts()['bundles']} bundles ({plan.n_missing} entries miss)")
+            if plan.n_dup_used:
+                b = int(plan.used[plan.entry(plan.first_dup)[0]])
+                raise _lib.ZcError(f"restore: bundle {b}: a chunk id twice in one bundle (entry {plan.first_dup})")
+        except Exception:
+            plan.close()
+            raise
+        return plan
+
+    def replay_device(self, plan, slot_ptrs, d_out, out_cap):
+        """zc_restore_replay: slot_ptrs[k] = the device pointer of the decoded
+        payload of bundle plan.used[k], slot_ptrs[n_used] = the instruction
+        stream the plan was parsed from.  Returns the restored length."""
+        L, ctx = self._comp._L, self._comp._ctx
+        ptrs = (ctypes.c_void_p * max(len(slot_ptrs), 1))(*[int(p) if p else None for p in slot_ptrs])
+        rc = L.zc_restore_replay(ctx, plan._live(), ptrs, len(slot_ptrs), d_out, int(out_cap))
+        _range_check(L, ctx, rc, "zc_restore_replay")
+        return plan.length
+
+    def restore_iterations(self, backup_data, iterations, chunk_index, payloads, out_cap):
+        """restoreIterations (backup_restorer.cc:109-136): backup_data restores
+        to the instruction stream of the iteration below, `iterations` times,
+        and that to the user data.  backup_data is uploaded once; then
+        iterations + 1 rounds of parse, plan, payloads(used, used_size) -- a
+        list of device pointers, one per used bundle -- and replay, each
+        round's output buffer the next round's stream.  Nothing per entry
+        crosses to the host.  Returns (device buffer, length): the user data,
+        the caller's to free (`free`); out_cap bounds every round's length."""
+        dec = BundleDecompressor(ctx=self._comp._ctx)
+        backup_data = bytes(backup_data)
+        d_stream, n = dec.alloc(max(len(backup_data), 1)), len(backup_data)
+        try:
+            dec.upload(d_stream, backup_data)
+            for _ in range(int(iterations) + 1):
+                with self.parse_device(d_stream, n) as ins, self.plan_device(ins, chunk_index) as plan:
+                    if plan.length > out_cap:
+                        raise _lib.ZcError(f"restore: {plan.length} bytes to restore, room for {out_cap}")
+                    ptrs = list(payloads(plan.used, plan.used_size))
+                    d_out = dec.alloc(max(plan.length, 1))
+                    try:
+                        # the round's bytes_to_emit runs are read from d_stream: it lives until the replay is done
+                        self.replay_device(plan, ptrs + [d_stream], d_out, plan.length)
+                    except Exception:
+                        dec.free(d_out)
+                        raise
+                    length = plan.length
+                dec.free(d_stream)
+                d_stream, n = d_out, length
+            out, d_stream = d_stream, None
+            return out, n
+        finally:
+            if d_stream is not None:
+                dec.free(d_stream)
+
+    def free(self, d_ptr):
+        """Frees a buffer restore_iterations returned."""
+        BundleDecompressor(ctx=self._comp._ctx).free(d_ptr)
+
+    def parse_last_stats(self):
+        """dict(hop_ms, exit_ms, chain_ms, emit_ms, tiles, chain_hops) of the last parse_device."""
+        L, ctx = self._comp._L, self._comp._ctx
+        ms = [ctypes.c_double() for _ in range(4)]
+        cnt = [ctypes.c_uint64() for _ in range(2)]
+        rc = L.zc_instr_last_stats(ctx, *[ctypes.byref(x) for x in ms + cnt])
+        _range_check(L, ctx, rc, "zc_instr_last_stats")
+        return dict(zip(("hop_ms", "exit_ms", "chain_ms", "emit_ms", "tiles", "chain_hops"),
+                        [x.value for x in ms + cnt]))
+
     def close(self):
         self._comp.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class InstructionSet:
+    """A zc_instr_set: a parsed BackupInstruction stream's entries in HBM
+    (`n_entries`, `n_messages`, `bytes_total`); fetch() is for tests and for
+    naming one entry in an error."""
+
+    def __init__(self, L, handle):
+        self._L, self._handle = L, handle
+        c = [ctypes.c_uint64() for _ in range(3)]
+        rc = L.zc_instr_set_counts(handle, *[ctypes.byref(x) for x in c])
+        if rc != _lib.ZC_OK:
+            raise _lib.ZcError(f"zc_instr_set_counts failed ({rc})")
+        self.n_entries, self.n_messages, self.bytes_total = (x.value for x in c)
+
+    def _live(self):
+        if self._handle is None:
+            raise _lib.ZcError("InstructionSet: closed")
+        return self._handle
+
+    def fetch(self, first=0, count=None):
+        """Entries [first, first + count) as parse_backup_data's array."""
+        from .bundle import INSTRUCTION_DTYPE
+        count = self.n_entries - first if count is None else count
+        out = np.zeros(max(count, 0), dtype=INSTRUCTION_DTYPE)
+        rc = self._L.zc_instr_set_fetch(self._live(), int(first), int(count), out.ctypes.data if count else None)
+        if rc != _lib.ZC_OK:
+            msg = self._L.zc_last_error(None) or b""
+            raise _lib.ZcError(f"zc_instr_set_fetch failed ({rc}): {msg.decode(errors='replace')}")
+        return out
+
+    def close(self):
+        if self._handle is not None:
+            self._L.zc_instr_set_destroy(self._handle)
+            self._handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class DevicePlan:
+    """A zc_restore_plan whose per-entry lists lie in HBM: the counters
+    (ResolvedStream's names), `used` / `used_size` per used bundle; `entry(e)`
+    gives one entry's (slot, off, size, dst); `slot`, `off`, `size`, `dst`
+    download all of them on first use."""
+    COUNTS = ("n_entries", "n_used", "length", "n_missing", "first_missing", "n_dup_used", "first_dup")
+
+    def __init__(self, L, handle):
+        self._L, self._handle, self._lists = L, handle, None
+        c = [ctypes.c_uint64() for _ in self.COUNTS]
+        rc = L.zc_restore_plan_counts(handle, *[ctypes.byref(x) for x in c])
+        if rc != _lib.ZC_OK:
+            raise _lib.ZcError(f"zc_restore_plan_counts failed ({rc})")
+        for name, x in zip(self.COUNTS, c):
+            setattr(self, name, x.value)
+        self.used, self.used_size = np.zeros(self.n_used, dtype=np.uint32), np.zeros(self.n_used, dtype=np.uint64)
+        if self.n_used:
+            rc = L.zc_restore_plan_used(handle, self.used.ctypes.data, self.used_size.ctypes.data)
+            if rc != _lib.ZC_OK:
+                raise _lib.ZcError(f"zc_restore_plan_used failed ({rc})")
+
+    def _live(self):
+        if self._handle is None:
+            raise _lib.ZcError("DevicePlan: closed")
+        return self._handle
+
+    def _fetch(self, *arrays):
+        rc = self._L.zc_restore_plan_fetch(self._live(), *[a.ctypes.data if a is not None and len(a) else None
+                                                           for a in arrays])
+        if rc != _lib.ZC_OK:
+            msg = self._L.zc_last_error(None) or b""
+            raise _lib.ZcError(f"zc_restore_plan_fetch failed ({rc}): {msg.decode(errors='replace')}")
+
+    def entry(self, e):
+        """(slot, off, size, dst) of entry e (zc_restore_plan_entry)."""
+        slot = ctypes.c_uint32()
+        v = [ctypes.c_uint64() for _ in range(3)]
+        rc = self._L.zc_restore_plan_entry(self._live(), int(e), ctypes.byref(slot), *[ctypes.byref(x) for x in v])
+        if rc != _lib.ZC_OK:
+            msg = self._L.zc_last_error(None) or b""
+            raise _lib.ZcError(f"zc_restore_plan_entry failed ({rc}): {msg.decode(errors='replace')}")
+        return (slot.value,) + tuple(x.value for x in v)
+
+    def _list(self, k):
+        if self._lists is None:
+            n = self.n_entries
+            lists = (np.zeros(n, dtype=np.uint32),) + tuple(np.zeros(n, dtype=np.uint64) for _ in range(3))
+            self._fetch(None, None, *lists)
+            self._lists = lists
+        return self._lists[k]
+
+    slot = property(lambda self: self._list(0))
+    off = property(lambda self: self._list(1))
+    size = property(lambda self: self._list(2))
+    dst = property(lambda self: self._list(3))
+
+    def close(self):
+        if self._handle is not None:
+            self._L.zc_restore_plan_destroy(self._handle)
+            self._handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class XzBodiesPayloads:
+    """A ready-made `payloads` of Restorer.restore_iterations for LZMA bundles
+    held in host memory: bodies[bundle number] = the bundle's xz stream
+    (zc_bundle_unseal's body).  A bundle is decoded on the device the first
+    time a round uses it (BundleDecompressor.decode_bodies) and its payload is
+    kept, so a bundle two iterations use is decoded once (`decodes` counts
+    them).  close() frees the payloads."""
+
+    def __init__(self, bodies, device=0, ctx=None):
+        self._bodies = bodies
+        self._dec = BundleDecompressor(device=device, ctx=ctx)
+        self._resident = {}  # bundle -> device pointer of its payload
+        self._buffers = []   # one device buffer per call that decoded something
+        self.decodes = 0
+
+    def __call__(self, used, used_size):
+        new = [(int(b), int(s)) for b, s in zip(used, used_size) if int(b) not in self._resident]
+        for b, _ in new:
+            if b not in self._bodies:
+                raise _lib.ZcError(f"restore: no body for bundle {b}")
+        if new:
+            bodies = [self._bodies[b] for b, _ in new]
+            out_off, pos = [], 0
+            for _, s in new:
+                out_off.append(pos)
+                pos += (s + 15) & ~15
+            # the payloads first, the staged bodies behind them
+            buf = self._dec.alloc(pos + max(self._dec.stage_size(bodies), 1))
+            try:
+                self._dec.decode_bodies(bodies, buf + pos, buf, out_off, [s for _, s in new])
+            except Exception:
+                self._dec.free(buf)
+                raise
+            self._buffers.append(buf)
+            for (b, _), o in zip(new, out_off):
+                self._resident[b] = buf + o
+            self.decodes += len(new)
+        return [self._resident[int(b)] for b in used]
+
+    def close(self):
+        if self._dec is not None:
+            for p in self._buffers:
+                self._dec.free(p)
+            self._buffers, self._resident = [], {}
+            self._dec.close()
+            self._dec = None
 
     def __enter__(self):
         return self
