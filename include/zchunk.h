@@ -63,6 +63,10 @@
  *   zc_parse_instructions_device, zc_restore_resolve_device, zc_restore_replay
  *                          one round of BackupRestorer::restoreIterations with the stream, its
  *                          entries and the plan in HBM                 backup_restorer.cc:109-136
+ *   zc_serialize_records_device
+ *                          outputInstruction for every record of a stream that lies in HBM, so
+ *                          that the shrink passes of backupFromFileHandle read their input
+ *                          where the pass before wrote it    backup_creator.cc:267-273, zutils.cc:137-166
  *   zc_device_alloc, zc_device_free, zc_upload
  *                          no counterpart: device memory for callers that have no HIP binding
  *                          of their own and keep decoded payloads in HBM
@@ -1056,6 +1060,35 @@ int zc_xz_encode_last_stats(const zc_ctx* ctx, double* match_ms, double* code_ms
  * fresh or regrown table starts from, so that the 32-bit generation's end is a few calls away;
  * a table cleared because the generations ran out starts from 0 again. */
 int zc_xz_encode_last_schedule(const zc_ctx* ctx, uint64_t* batches, uint64_t* max_rounds, uint32_t* generation);
+
+/* ---- the records serialized on the device ----
+ * zc_serialize_records for a stream that lies in HBM, its output left in HBM: the same bytes (one
+ * message per record: 0x12 and the stream's bytes [offset, offset + size) for kind ZC_BYTES, 0x0a
+ * and the 24-byte chunk id for every other kind value), without a host copy per bytes_to_emit.
+ * The output is a stream zc_chunk_device can chunk where it lies, which is the input of
+ * backupFromFileHandle's shrink passes (zutils.cc:137-166).  Callers detect these entry points by
+ * their symbols (the ABI version stays 5). */
+/* The length of the records' stream: what zc_serialize_records reports as needed, with no
+ * context and no stream.  Host bookkeeping only.  ZC_ERR_ARG with a message in
+ * zc_last_error(NULL): NULL bytes, NULL recs with n > 0. */
+int zc_serialized_size(const zc_record* recs, size_t n, uint64_t* bytes);
+/* recs: n records in host memory (uploaded in one copy); d_stream: the device buffer of
+ * stream_len bytes their offsets refer to (given here, not taken from the context's last
+ * stream); d_out: room for out_cap bytes in device memory, which must not overlap d_stream.
+ * *n_out = the bytes written.  Only [d_out, d_out + *n_out) is written.  ZC_ERR_ARG with a
+ * message, before any device work and with the output untouched: NULL n_out, NULL recs with
+ * n > 0, NULL d_stream with stream_len > 0, NULL d_out with out_cap > 0, n >= 2^32 - 1, a
+ * ZC_BYTES record with offset + size > stream_len (the message names the record's index), and
+ * out_cap smaller than the stream, when *n_out = the bytes needed.  n == 0 is ZC_OK, writes
+ * nothing and sets *n_out = 0.  Runs on the context's stream after the work queued on the default
+ * stream so far; complete on return. */
+int zc_serialize_records_device(zc_ctx* ctx, const zc_record* recs, size_t n, const void* d_stream,
+                                uint64_t stream_len, void* d_out, uint64_t out_cap, uint64_t* n_out);
+/* The context's last zc_serialize_records_device: time on the stream of the records' upload, of
+ * the length kernel with its scans, and of the write and copy kernels; the messages assembled
+ * whole in LDS and the 64 KiB copies the longer payloads took.  A NULL output is skipped. */
+int zc_serialize_last_stats(const zc_ctx* ctx, double* upload_ms, double* size_ms, double* write_ms,
+                            uint64_t* staged_msgs, uint64_t* copy_pieces);
 
 int zc_abi_version(void);
 /* digest of the sources this library was built from (zbackup_amd/_build.py

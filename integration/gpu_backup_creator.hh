@@ -342,6 +342,147 @@ public:
   }
 };
 
+/// backupFromFileHandle (zutils.cc:89-182) for data that already lies in HBM,
+/// with the backup data kept there through the shrink loop (zutils.cc:137-166):
+/// every pass is zc_chunk_device on the buffer the pass before wrote with
+/// zc_serialize_records_device, on GpuChunkIndex's context, so a pass matches
+/// the chunks the passes before it added.  Per pass the host sees the records;
+/// the NEW chunks' bytes are gathered on the device (zc_bundle_gather) and read
+/// once, for Writer::add; no bytes_to_emit payload and no intermediate stream
+/// comes to the host, and only the final stream is read back.  The whole-stream
+/// SHA-256 stays with the caller, who has the data (zc_sha256_*).
+///
+///   GpuDeviceBackup deviceBackup( gpuIndex, chunkStorageWriter );
+///   deviceBackup.backup( d_data, n, info );   // backup_data, iterations, size
+///   info.set_sha256( ... ); chunkStorageWriter.commit(); ...
+class GpuDeviceBackup: NoCopy
+{
+  zc_ctx * ctx;
+  ChunkStorage::Writer & chunkStorageWriter;
+
+  // a device buffer of this call
+  struct Buffer: NoCopy
+  {
+    zc_ctx * ctx;
+    void * p;
+    uint64_t size;
+    explicit Buffer( zc_ctx * c ): ctx( c ), p( 0 ), size( 0 ) {}
+    void make( uint64_t bytes )
+    {
+      drop();
+      zcCheck( zc_device_alloc( ctx, bytes, &p ), ctx, "zc_device_alloc" );
+      size = bytes;
+    }
+    void drop()
+    {
+      if ( p )
+        zc_device_free( ctx, p );
+      p = 0;
+      size = 0;
+    }
+    void swap( Buffer & other )
+    {
+      std::swap( p, other.p );
+      std::swap( size, other.size );
+    }
+    ~Buffer() { drop(); }
+  };
+
+  // n device bytes to the host, one read through the range reader's staging buffer
+  void download( void const * d, uint64_t n, string & out )
+  {
+    out.resize( n );
+    if ( !n )
+      return;
+    zc_range_index * one = 0;
+    uint32_t slot = 0;
+    uint64_t zero = 0;
+    zcCheck( zc_range_index_create( ctx, &n, 1, &slot, &zero, &n, 1, &one ), ctx, "zc_range_index_create" );
+    int rc = zc_range_set_slot( one, 0, d );
+    if ( rc == ZC_OK )
+      rc = zc_range_read_host( ctx, one, &zero, &n, 1, &out[ 0 ], &zero );
+    string err = rc == ZC_OK ? string() : string( zc_last_error( ctx ) );
+    zc_range_index_destroy( one );
+    if ( rc != ZC_OK )
+      throw std::runtime_error( "GpuDeviceBackup: reading from the device: " + err );
+  }
+
+  // One BackupCreator's life on the stream [d, d + n): the records, Writer::add
+  // for every NEW chunk (saveChunkToSave, backup_creator.cc:124-139), the
+  // instruction stream into `out`
+  void pass( void const * d, uint64_t n, Buffer & out )
+  {
+    zcCheck( zc_reset( ctx ), ctx, "zc_reset" );  // a new stream on the shared index
+    zcCheck( zc_chunk_device( ctx, d, n ), ctx, "zc_chunk_device" );
+    std::vector< zc_record > records( zc_record_count( ctx ) + 1 );
+    size_t count = 0;
+    zcCheck( zc_get_records( ctx, records.data(), records.size(), &count ), ctx, "zc_get_records" );
+    std::vector< uint64_t > off, size;
+    uint64_t total = 0;
+    for ( size_t i = 0; i < count; ++i )
+      if ( records[ i ].kind == ZC_CHUNK_NEW )
+      {
+        off.push_back( records[ i ].offset );
+        size.push_back( records[ i ].size );
+        total += records[ i ].size;
+      }
+    if ( !off.empty() )
+    {
+      Buffer payload( ctx );
+      payload.make( total );
+      zcCheck( zc_bundle_gather( ctx, d, off.data(), size.data(), off.size(), payload.p ), ctx, "zc_bundle_gather" );
+      string bytes;
+      download( payload.p, total, bytes );
+      uint64_t at = 0;
+      for ( size_t i = 0; i < count; ++i )
+        if ( records[ i ].kind == ZC_CHUNK_NEW )
+        {
+          ChunkId id;
+          memcpy( id.cryptoHash, records[ i ].sha1, sizeof( id.cryptoHash ) );
+          id.rollingHash = records[ i ].rolling;
+          chunkStorageWriter.add( id, bytes.data() + at, records[ i ].size );
+          at += records[ i ].size;
+        }
+    }
+    uint64_t need = 0, wrote = 0;
+    if ( zc_serialized_size( records.data(), count, &need ) != ZC_OK )
+      throw std::runtime_error( string( "zc_serialized_size: " ) + zc_last_error( 0 ) );
+    out.make( need );
+    zcCheck( zc_serialize_records_device( ctx, records.data(), count, n ? d : 0, n, out.p, need, &wrote ), ctx,
+             "zc_serialize_records_device" );
+  }
+
+public:
+  GpuDeviceBackup( GpuChunkIndex & index, ChunkStorage::Writer & writer ):
+    ctx( index.context() ), chunkStorageWriter( writer ) {}
+
+  /// d_data: n bytes in device memory, 16-byte aligned (zc_chunk_device).
+  /// BackupInfoT: zbackup's BackupInfo, or anything with set_size,
+  /// iterations / set_iterations and mutable_backup_data.
+  template< class BackupInfoT >
+  void backup( void const * d_data, uint64_t n, BackupInfoT & info )
+  {
+    Buffer serialized( ctx ), newGen( ctx );
+    pass( d_data, n, serialized );
+    info.set_size( n );
+    // Shrink the serialized data iteratively until it wouldn't shrink anymore
+    for ( ; ; )
+    {
+      pass( serialized.p, serialized.size, newGen );
+      if ( newGen.size < serialized.size )
+      {
+        serialized.swap( newGen );  // the pass is complete: nothing reads the older generation again
+        newGen.drop();
+        info.set_iterations( info.iterations() + 1 );
+      }
+      else
+        break;
+    }
+    download( serialized.p, serialized.size, *info.mutable_backup_data() );
+    zcCheck( zc_reset( ctx ), ctx, "zc_reset" );  // the context refers to no buffer of this call
+  }
+};
+
 /// lzo1x_1 of finished bundles on the GPU, for Bundle::Creator::write
 /// (bundle.cc:96-155) when the selected compression is "lzo1x_1": the framed
 /// bytes equal what LZO1X_1_Encoder writes (compression.cc:435-466, 586-606),

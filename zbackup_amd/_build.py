@@ -15,7 +15,7 @@ SOURCES = [os.path.join(CSRC, "zc_kernels.hip"), os.path.join(CSRC, "zc_engine.c
            os.path.join(CSRC, "zc_meta.hip"), os.path.join(CSRC, "zc_range.hip"),
            os.path.join(CSRC, "zc_index.hip"), os.path.join(CSRC, "zc_xz.hip"),
            os.path.join(CSRC, "zc_xzenc.hip"), os.path.join(CSRC, "zc_resolve.hip"),
-           os.path.join(CSRC, "zc_instr.hip")]
+           os.path.join(CSRC, "zc_instr.hip"), os.path.join(CSRC, "zc_ser.hip")]
 # host-only sources (no device code; built by the host compiler with x86 intrinsics)
 HOST_ONLY = {"zc_sha256.cpp"}
 HEADERS = [os.path.join(CSRC, "zc_device.h"), os.path.join(CSRC, "zc_lzo_core.h"),
@@ -25,6 +25,7 @@ HEADERS = [os.path.join(CSRC, "zc_device.h"), os.path.join(CSRC, "zc_lzo_core.h"
            os.path.join(CSRC, "zc_index_core.h"), os.path.join(CSRC, "zc_xz_core.h"),
            os.path.join(CSRC, "zc_xz_dev.h"), os.path.join(CSRC, "zc_xzenc_core.h"),
            os.path.join(CSRC, "zc_resolve_core.h"), os.path.join(CSRC, "zc_instr_core.h"),
+           os.path.join(CSRC, "zc_scan_body.h"), os.path.join(CSRC, "zc_ser_core.h"),
            os.path.join(ROOT, "include", "zchunk.h")]
 ARCH = os.environ.get("ZC_OFFLOAD_ARCH", "gfx950")
 

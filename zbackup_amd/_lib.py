@@ -40,7 +40,7 @@ EXPORTS = ["zc_create", "zc_destroy", "zc_seed_index", "zc_get_input_buffer",
            "zc_restore_plan_fetch", "zc_restore_plan_destroy", "zc_resolve_last_stats",
            "zc_parse_instructions_device", "zc_instr_set_counts", "zc_instr_set_fetch", "zc_instr_set_destroy",
            "zc_instr_last_stats", "zc_restore_resolve_device", "zc_restore_plan_entry", "zc_restore_plan_used",
-           "zc_restore_replay"]
+           "zc_restore_replay", "zc_serialized_size", "zc_serialize_records_device", "zc_serialize_last_stats"]
 (ZC_INDEX_OK, ZC_INDEX_BAD_SIZE, ZC_INDEX_BAD_PADDING, ZC_INDEX_TRUNCATED, ZC_INDEX_BAD_VERSION, ZC_INDEX_BAD_MESSAGE,
  ZC_INDEX_BAD_BUNDLE_ID, ZC_INDEX_BAD_CHUNK_ID, ZC_INDEX_BAD_ADLER) = range(9)
 INDEX_STATUS_NAMES = {0: "ok", 1: "bad file size", 2: "bad padding", 3: "truncated", 4: "unsupported version",
@@ -316,6 +316,10 @@ def load(path=LIB_PATH):
         "zc_restore_plan_entry": (i32, [vp, u64, ctypes.POINTER(u32)] + [ctypes.POINTER(u64)] * 3),
         "zc_restore_plan_used": (i32, [vp, vp, vp]),
         "zc_restore_replay": (i32, [vp, vp, vp, sz, vp, u64]),
+        # the records serialized in HBM: (recs, n, &bytes); (ctx, recs, n, d_stream, stream_len, d_out, out_cap, &n_out)
+        "zc_serialized_size": (i32, [vp, sz, ctypes.POINTER(u64)]),
+        "zc_serialize_records_device": (i32, [vp, vp, sz, vp, u64, vp, u64, ctypes.POINTER(u64)]),
+        "zc_serialize_last_stats": (i32, [vp] + [ctypes.POINTER(ctypes.c_double)] * 3 + [ctypes.POINTER(u64)] * 2),
         "zc_device_alloc": (i32, [vp, u64, ctypes.POINTER(vp)]),
         "zc_device_free": (i32, [vp, vp]),
         "zc_upload": (i32, [vp, vp, vp, u64]),

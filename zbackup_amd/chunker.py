@@ -70,6 +70,18 @@ def _seed_array(sha1, rolling, size):
     return rec
 
 
+def serialized_size(recs):
+    """zc_serialized_size: the length of the BackupInstruction stream of a
+    RECORD_DTYPE array (host bookkeeping: no context, no device)."""
+    recs = np.ascontiguousarray(recs, dtype=RECORD_DTYPE)
+    need = ctypes.c_uint64()
+    L = _lib.load()
+    rc = L.zc_serialized_size(recs.ctypes.data if len(recs) else None, len(recs), ctypes.byref(need))
+    if rc != _lib.ZC_OK:  # a call without a context: the message is the thread's
+        raise _lib.ZcError(f"zc_serialized_size failed ({rc}): {L.zc_last_error(None).decode(errors='replace')}")
+    return need.value
+
+
 def anchor_def(chunk_max_size):
     """zc_anchor_def: the anchor definition this build's metadata carries for W."""
     return int(_lib.load().zc_anchor_def(int(chunk_max_size)))
@@ -235,6 +247,107 @@ class BackupCreator:
         the same pipeline as chunk_device (zutils.cc:100-124 read loop + finish)."""
         self._new_stream()
         _check(self._L, self._ctx, self._L.zc_chunk_host(self._ctx, ctypes.c_void_p(ptr), n), "zc_chunk_host")
+
+    # -- the backup data kept in HBM -------------------------------------------
+    def serialize_device(self, recs, d_stream, stream_len):
+        """zc_serialize_records_device: the BackupInstruction stream of `recs` (a
+        RECORD_DTYPE array whose offsets refer to the `stream_len` bytes at device
+        pointer `d_stream`), written into a device buffer of its own.  Returns
+        (device pointer, bytes); the caller hands the pointer to free_device."""
+        recs = np.ascontiguousarray(recs, dtype=RECORD_DTYPE)
+        need = serialized_size(recs)
+        d_out = ctypes.c_void_p()
+        _check(self._L, self._ctx, self._L.zc_device_alloc(self._ctx, need, ctypes.byref(d_out)), "zc_device_alloc")
+        wrote = ctypes.c_uint64()
+        rc = self._L.zc_serialize_records_device(self._ctx, recs.ctypes.data, len(recs),
+                                                 ctypes.c_void_p(d_stream) if stream_len else None, stream_len,
+                                                 d_out, need, ctypes.byref(wrote))
+        if rc != _lib.ZC_OK:
+            msg = self._L.zc_last_error(self._ctx) or b""
+            self._L.zc_device_free(self._ctx, d_out)
+            raise _lib.ZcError(f"zc_serialize_records_device failed ({rc}): {msg.decode(errors='replace')}")
+        return d_out.value, wrote.value
+
+    def free_device(self, d_ptr):
+        """zc_device_free of a buffer serialize_device returned."""
+        _check(self._L, self._ctx, self._L.zc_device_free(self._ctx, ctypes.c_void_p(d_ptr)), "zc_device_free")
+
+    def serialize_stats(self):
+        """zc_serialize_last_stats as a dict: upload_ms, size_ms, write_ms (device
+        time of the last serialize_device's steps), staged_msgs, copy_pieces."""
+        ms = [ctypes.c_double() for _ in range(3)]
+        cnt = [ctypes.c_uint64() for _ in range(2)]
+        _check(self._L, self._ctx,
+               self._L.zc_serialize_last_stats(self._ctx, *[ctypes.byref(v) for v in ms + cnt]),
+               "zc_serialize_last_stats")
+        names = ("upload_ms", "size_ms", "write_ms", "staged_msgs", "copy_pieces")
+        return {k: v.value for k, v in zip(names, ms + cnt)}
+
+    def _download(self, d_ptr, n):
+        """`n` bytes of device memory as bytes: one read through the range reader's staging buffer."""
+        if not n:
+            return b""
+        one, zero, slot = np.array([n], dtype=np.uint64), np.zeros(1, dtype=np.uint64), np.zeros(1, dtype=np.uint32)
+        idx = ctypes.c_void_p()
+        _check(self._L, self._ctx,
+               self._L.zc_range_index_create(self._ctx, one.ctypes.data, 1, slot.ctypes.data, zero.ctypes.data,
+                                             one.ctypes.data, 1, ctypes.byref(idx)), "zc_range_index_create")
+        out = np.empty(n, dtype=np.uint8)
+        try:
+            rc = self._L.zc_range_set_slot(idx, 0, ctypes.c_void_p(d_ptr))
+            if rc == _lib.ZC_OK:
+                rc = self._L.zc_range_read_host(self._ctx, idx, zero.ctypes.data, one.ctypes.data, 1,
+                                                out.ctypes.data, zero.ctypes.data)
+            _check(self._L, self._ctx, rc, "zc_range_read_host")
+        finally:
+            self._L.zc_range_index_destroy(idx)
+        return out.tobytes()
+
+    def backup_device(self, ptr, n, on_new=None):
+        """The backup of `n` bytes at device pointer `ptr` with its backup data kept
+        in HBM: chunk_device, serialize_device, then backupFromFileHandle's
+        shrink loop (zutils.cc:137-166) -- reset(), chunk_device on the
+        serialized buffer where it lies, on this context, so that a pass matches
+        the chunks the passes before it added; the new generation is kept only
+        when it is strictly shorter, else the loop ends.  Only the final stream
+        comes to the host.
+
+        on_new(new_records, d_stream_ptr, pass_no) is called once per pass, the
+        last, discarded one included (its chunks were added like the others'),
+        with the pass's ZC_CHUNK_NEW records and the device buffer their offsets
+        refer to, which stays valid during the call: the place to
+        zc_bundle_gather their payloads.  Pass 0 is the user's stream.
+
+        Returns (backup_data, iterations, pass_lengths): pass_lengths[k] is the
+        length of the stream pass k wrote.  The context is reset() at the end:
+        no buffer it refers to outlives the call."""
+        def one_pass(d_stream, length, pass_no):
+            self.chunk_device(d_stream, length)
+            recs = self.records()
+            if on_new is not None:
+                on_new(recs[recs["kind"] == _lib.ZC_CHUNK_NEW], d_stream, pass_no)
+            return self.serialize_device(recs, d_stream, length)
+
+        cur, cur_n = one_pass(ptr, n, 0)
+        lengths, iterations = [cur_n], 0
+        try:
+            while True:
+                self.reset()
+                nxt, nxt_n = one_pass(cur, cur_n, len(lengths))
+                lengths.append(nxt_n)
+                if nxt_n < cur_n:
+                    self.free_device(cur)  # the next generation is serialized: nothing reads this one again
+                    cur, cur_n = nxt, nxt_n
+                    iterations += 1
+                else:
+                    self.free_device(nxt)
+                    break
+            data = self._download(cur, cur_n)
+        finally:
+            self._L.zc_reset(self._ctx)
+            self._L.zc_device_free(self._ctx, ctypes.c_void_p(cur))
+        self._new_stream()
+        return data, iterations, lengths
 
     # -- results -------------------------------------------------------------
     def _held(self):

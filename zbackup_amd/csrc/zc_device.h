@@ -721,6 +721,29 @@ void instr_set_view(const zc_instr_set* set, int* device, const uint32_t** d_ins
 int instr_set_fetch(const zc_instr_set* set, uint64_t first, uint64_t count, zc_instruction* out, std::string& err);
 void instr_set_destroy(zc_instr_set* set);
 
+// zc_ser.hip: records to their BackupInstruction stream in HBM (zc_ser_core.h).
+// ser_measure and ser_validate check what the host can see (no device, no
+// context); each call returns a zc_status with its message in `err`.
+struct SerScratch;
+struct SerTimes {
+  double upload_ms, size_ms, write_ms;  // the records' copy; the lengths and their scans; the write and copy kernels
+  uint64_t staged_msgs, copy_pieces;    // messages assembled whole in LDS; 64 KiB copies of the other payloads
+};
+struct SerPlan {
+  uint64_t bytes, staged, pieces;  // the stream's length; SerTimes' two counts
+};
+SerScratch* ser_scratch_new();
+void ser_scratch_free(SerScratch* s);
+const SerTimes* ser_times(const SerScratch* s);
+// stream_len: NULL, or the length every ZC_BYTES record's range is checked against
+int ser_measure(const zc_record* recs, size_t n, const uint64_t* stream_len, SerPlan* plan, std::string& err);
+// *n_out: the stream's length, also when out_cap is too small for it
+int ser_validate(const zc_record* recs, size_t n, const void* d_stream, uint64_t stream_len, const void* d_out,
+                 uint64_t out_cap, uint64_t* n_out, SerPlan* plan, std::string& err);
+// what ser_validate let through; ev_in orders the context stream after the legacy default stream
+int ser_write(SerScratch* s, int device, const zc_record* recs, size_t n, const void* d_stream, void* d_out,
+              const SerPlan& plan, hipEvent_t ev_in, hipStream_t st, std::string& err);
+
 // zc_xz.hip: LZMA bundles, xz streams decoded to their payloads (zc_xz_core.h).
 // xz_validate checks what the host can see (no device, no context); xz_decode
 // returns a zc_status with its message in `err`.

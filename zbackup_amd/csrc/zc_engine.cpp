@@ -545,6 +545,7 @@ struct zc_ctx {
   IndexScratch* index = nullptr;  // index files' buffers (zc_index.hip), made on first use
   ResolveScratch* rs = nullptr;   // the chunk index's build and resolve buffers (zc_resolve.hip), made on first use
   InstrScratch* instr = nullptr;  // the device parse's exits and tile tables (zc_instr.hip), made on first use
+  SerScratch* ser = nullptr;      // the device serializer's records and positions (zc_ser.hip), made on first use
   XzScratch* xz = nullptr;        // LZMA bundles' buffers (zc_xz.hip), made on first use
   XzEncScratch* xzenc = nullptr;  // the encoder's tables and candidates (zc_xzenc.hip), made on first use
 
@@ -3394,6 +3395,7 @@ int zc_destroy(zc_ctx* c) {
     index_scratch_free(c->index);
     resolve_scratch_free(c->rs);
     if (c->instr) instr_scratch_free(c->instr);
+    if (c->ser) ser_scratch_free(c->ser);
     xz_scratch_free(c->xz);
     xzenc_scratch_free(c->xzenc);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -4948,6 +4950,57 @@ int zc_instr_last_stats(const zc_ctx* c, double* hop_ms, double* exit_ms, double
   if (emit_ms) *emit_ms = t.emit_ms;
   if (tiles) *tiles = t.tiles;
   if (chain_hops) *chain_hops = t.chain_hops;
+  return ZC_OK;
+}
+
+// ---- the records serialized in HBM (zc_ser.hip) ----
+
+int zc_serialized_size(const zc_record* recs, size_t n, uint64_t* bytes) {
+  if (!bytes) return host_arg_error("zc_serialized_size: null size pointer");
+  std::string err;
+  SerPlan plan;
+  const int rc = ser_measure(recs, n, nullptr, &plan, err);
+  if (rc != ZC_OK) return host_arg_error(("zc_serialized_size: " + err).c_str());
+  *bytes = plan.bytes;
+  g_host_err.clear();
+  return ZC_OK;
+}
+
+int zc_serialize_records_device(zc_ctx* c, const zc_record* recs, size_t n, const void* d_stream,
+                                uint64_t stream_len, void* d_out, uint64_t out_cap, uint64_t* n_out) {
+  ZC_LOCK(c);
+  std::string err;
+  SerPlan plan;
+  const int checked = ser_validate(recs, n, d_stream, stream_len, d_out, out_cap, n_out, &plan, err);
+  if (checked != ZC_OK) return ctx_arg_error(c, ("zc_serialize_records_device: " + err).c_str());
+  if (!c) return ctx_arg_error(c, "zc_serialize_records_device: null context");
+  int rc;
+  try {
+    DeviceGuard g(c->device);
+    if (!c->ser) c->ser = ser_scratch_new();
+    rc = ser_write(c->ser, c->device, recs, n, d_stream, d_out, plan, c->ev_in, c->stream, err);
+  } catch (const ZcError& e) {
+    return fail(c, e);
+  } catch (const std::bad_alloc&) {
+    return fail(c, ZcError{ZC_ERR_NOMEM, "host allocation failed"});
+  }
+  if (rc != ZC_OK)
+    c->err = "zc_serialize_records_device: " + err;
+  else
+    c->err.clear();
+  return rc;
+}
+
+int zc_serialize_last_stats(const zc_ctx* c, double* upload_ms, double* size_ms, double* write_ms,
+                            uint64_t* staged_msgs, uint64_t* copy_pieces) {
+  ZC_LOCK(c);
+  if (!c) return host_arg_error("zc_serialize_last_stats: null context");
+  const SerTimes t = c->ser ? *ser_times(c->ser) : SerTimes{};
+  if (upload_ms) *upload_ms = t.upload_ms;
+  if (size_ms) *size_ms = t.size_ms;
+  if (write_ms) *write_ms = t.write_ms;
+  if (staged_msgs) *staged_msgs = t.staged_msgs;
+  if (copy_pieces) *copy_pieces = t.copy_pieces;
   return ZC_OK;
 }
 

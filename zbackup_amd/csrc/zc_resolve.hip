@@ -8,7 +8,7 @@
 // collection's exact id table (zc_gc_core.h), kept with each record's payload
 // offset, and a resolve is one probe per chunk_to_emit (zc_resolve_core.h).
 //
-//   build     zc_rs_tile_sums / zc_rs_tile_scan / zc_rs_scan_write
+//   build     zc_scan_tile_sums / zc_scan_tile_scan / zc_scan_write (zc_scan_body.h)
 //                                 the running sum of `sizes` over all records
 //             zc_rs_place         records into processing order (zc_gc.hip): per position
 //                                 its id, size, bundle and payload offset = the running sum
@@ -54,6 +54,7 @@
 #include "zc_device.h"
 #include "zc_lzo_core.h"
 #include "zc_resolve_core.h"
+#include "zc_scan_body.h"
 
 static_assert(sizeof(zc_instruction) == 48, "zc_instruction is read as twelve 32-bit words");
 static_assert(ZC_INSTR_CHUNK == zcrs::kKindChunk && ZC_INSTR_BYTES == zcrs::kKindBytes, "entry kinds");
@@ -62,9 +63,8 @@ namespace zc {
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr uint32_t kTileItems = 4;               // values per thread of a scan tile
-constexpr uint32_t kTile = kBlock * kTileItems;  // values per tile
+constexpr int kBlock = zcscan::kBlock;
+constexpr uint32_t kTile = zcscan::kTile;  // values per scan tile (zc_scan_body.h)
 constexpr uint64_t kCountLimit = 0xffffffffull;  // counts stay below 2^32 - 1
 
 // what the kernels report, one copy on the device
@@ -79,80 +79,6 @@ struct RsDev {
 
 __device__ inline void note_probe(RsDev* dev, uint32_t longest) {
   if (longest) atomicMax(&dev->max_probe, longest);
-}
-
-// exclusive prefix of v over the block's 256 threads (a shuffle scan per wave,
-// the four waves' sums through LDS); *sum: the block's total
-__device__ inline uint64_t block_prefix(uint64_t v, uint64_t* ls, uint64_t* sum) {
-  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint64_t inc = v;
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint64_t up = __shfl_up((unsigned long long)inc, d, 64);
-    if ((int)lane >= d) inc += up;
-  }
-  if (lane == 63) ls[wave] = inc;
-  __syncthreads();
-  uint64_t before = 0, all = 0;
-  for (uint32_t w = 0; w < kBlock / 64; w++) {
-    if (w < wave) before += ls[w];
-    all += ls[w];
-  }
-  __syncthreads();  // ls may be reused
-  *sum = all;
-  return before + inc - v;
-}
-
-template <class T>
-__global__ __launch_bounds__(kBlock) void zc_rs_tile_sums(const T* __restrict__ src, uint64_t n, uint32_t ntiles,
-                                                          uint64_t* __restrict__ tsum) {
-  __shared__ uint64_t ls[kBlock / 64];
-  for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    const uint64_t base = (uint64_t)tile * kTile + threadIdx.x * kTileItems;
-    uint64_t v = 0;
-    for (uint32_t k = 0; k < kTileItems; k++)
-      if (base + k < n) v += src[base + k];
-    uint64_t sum;
-    (void)block_prefix(v, ls, &sum);
-    if (threadIdx.x == 0) tsum[tile] = sum;
-  }
-}
-
-// one workgroup: the tiles' sums to exclusive prefixes, 256 at a time
-__global__ __launch_bounds__(kBlock) void zc_rs_tile_scan(uint64_t* __restrict__ tsum, uint32_t ntiles,
-                                                          unsigned long long* __restrict__ total) {
-  __shared__ uint64_t ls[kBlock / 64];
-  uint64_t carry = 0;
-  for (uint32_t base = 0; base < ntiles; base += kBlock) {
-    const uint32_t i = base + threadIdx.x;
-    const uint64_t v = i < ntiles ? tsum[i] : 0;
-    uint64_t sum;
-    const uint64_t pre = block_prefix(v, ls, &sum);
-    if (i < ntiles) tsum[i] = carry + pre;
-    carry += sum;
-  }
-  if (threadIdx.x == 0) *total = carry;
-}
-
-// out[i] = the sum of src[0 .. i); out[n] = the total (tail != 0)
-template <class T>
-__global__ __launch_bounds__(kBlock) void zc_rs_scan_write(const T* __restrict__ src, uint64_t n, uint32_t ntiles,
-                                                           const uint64_t* __restrict__ tsum,
-                                                           uint64_t* __restrict__ out, int tail) {
-  __shared__ uint64_t ls[kBlock / 64];
-  for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    const uint64_t base = (uint64_t)tile * kTile + threadIdx.x * kTileItems;
-    uint64_t v = 0;
-    for (uint32_t k = 0; k < kTileItems; k++)
-      if (base + k < n) v += src[base + k];
-    uint64_t sum;
-    uint64_t at = tsum[tile] + block_prefix(v, ls, &sum);
-    for (uint32_t k = 0; k < kTileItems; k++)
-      if (base + k < n) {
-        out[base + k] = at;
-        at += src[base + k];
-        if (tail && base + k == n - 1) out[n] = at;
-      }
-  }
 }
 
 __global__ __launch_bounds__(kBlock) void zc_rs_place(const uint64_t* __restrict__ ids,
@@ -485,9 +411,9 @@ int scan(ResolveScratch* s, const T* src, uint64_t n, uint64_t* out, bool tail, 
   if (!ntiles) return ZC_OK;  // the caller zeroed *d_total
   RCK(s->tsum.ensure(ntiles));
   const int gt = (int)std::min<uint64_t>(ntiles, (uint64_t)s->cus * 16);
-  zc_rs_tile_sums<T><<<gt, kBlock, 0, st>>>(src, n, ntiles, s->tsum.p);
-  zc_rs_tile_scan<<<1, kBlock, 0, st>>>(s->tsum.p, ntiles, d_total);
-  zc_rs_scan_write<T><<<gt, kBlock, 0, st>>>(src, n, ntiles, s->tsum.p, out, tail ? 1 : 0);
+  zcscan::zc_scan_tile_sums<T><<<gt, kBlock, 0, st>>>(src, n, ntiles, s->tsum.p);
+  zcscan::zc_scan_tile_scan<<<1, kBlock, 0, st>>>(s->tsum.p, ntiles, d_total);
+  zcscan::zc_scan_write<T><<<gt, kBlock, 0, st>>>(src, n, ntiles, s->tsum.p, out, tail ? 1 : 0);
   return ZC_OK;
 }
 
