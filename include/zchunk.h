@@ -180,6 +180,20 @@ typedef struct zc_ctx zc_ctx;
 
 int zc_create(zc_ctx** out, uint32_t chunk_max_size, int device, uint32_t flags);
 int zc_destroy(zc_ctx* ctx);
+/* KNOWN DIVERGENCE from the reference, the only one: the index holds W-byte
+ * chunks only.  Entries whose size is not chunk.max_size are skipped by
+ * zc_seed_index and zc_seed_index_meta, and the sub-W chunks a context's own
+ * streams save (a flush before a match, a stream's tail) are reported as NEW
+ * records but never registered.  ChunkIndex::findChunk compares the rolling
+ * hash and the 16 SHA-1 bytes and never the size (chunk_index.cc:119-143), so
+ * the reference would match a W-byte window with an indexed chunk of another
+ * length that had the same 64-bit rolling hash and the same SHA-1 prefix: a
+ * collision of both hashes between byte strings of different lengths.
+ * Registering such ids would put every sub-W chunk of a repository (each
+ * backup's tail) into the by-value set, whose presence sends every stream
+ * through the per-byte exact screen instead of the anchor probe.
+ * tests/golden/refpin_divergent/ records the reference's verdict on such an
+ * index; tests/test_gpu_refpin.py asserts what the engine gives instead. */
 int zc_seed_index(zc_ctx* ctx, const zc_seed* seeds, size_t n);
 /* ABI 5.  Seed the ids of an existing index (as zc_seed_index) together with the
  * metadata kept for them: an id whose entry in meta[0, nm) matches its full

@@ -117,6 +117,46 @@ def chunk(data, W, seeds=(), feed_max=0, ref=False):
     return recs
 
 
+def parse_record_lines(text):
+    """Record lines `N|D|B <offset> <size> <rolling> <sha1_16>` and refused-add
+    lines `X <record index>` -> (record tuples, refused indices)."""
+    recs, refused = [], []
+    for line in text.splitlines():
+        if line[:2] == "X ":
+            refused.append(int(line[2:]))
+        elif line[:2] in ("N ", "D ", "B "):
+            k, off, size, h, sha = line.split()
+            recs.append((k, int(off), int(size), int(h, 16), sha))
+    return recs, refused
+
+
+def chunk_refbc(data, W, seeds=(), feed_max=0):
+    """Run the reference's OWN BackupCreator and ChunkIndex (_ref/zbc_ref_cli,
+    built by `make ref` where the reference sources exist) over `data`.  seeds:
+    (sha1_16, rolling, size) tuples, registered in order through
+    ChunkIndex::addChunk.  Returns (record tuples as chunk() gives them, indices
+    of the NEW records whose Writer::add returned false)."""
+    exe = os.path.join(HERE, "_ref", "zbc_ref_cli")
+    if not os.path.exists(exe):
+        build(ref=True)
+    data = np.ascontiguousarray(data, dtype=np.uint8)
+    blob = b"".join(bytes(sha16)[:16] + int(rolling).to_bytes(8, "little") + int(size).to_bytes(4, "little")
+                    for sha16, rolling, size in seeds)
+    args = [exe, str(W), "-", str(feed_max)]
+    if blob:
+        import tempfile
+        with tempfile.NamedTemporaryFile(suffix=".seeds") as f:
+            f.write(blob)
+            f.flush()
+            args[2] = f.name
+            out = subprocess.run(args, input=data.tobytes(), capture_output=True)
+    else:
+        out = subprocess.run(args, input=data.tobytes(), capture_output=True)
+    if out.returncode:
+        raise RuntimeError(f"zbc_ref_cli failed ({out.returncode}): {out.stderr.decode()[-500:]}")
+    return parse_record_lines(out.stdout.decode())
+
+
 RECORD_DTYPE = np.dtype([("offset", "<u8"), ("size", "<u4"), ("kind", "<u4"),
                          ("rolling", "<u8"), ("sha1", "u1", (16,))])
 OPT_PREFILTER = 1

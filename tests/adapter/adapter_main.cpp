@@ -9,7 +9,9 @@
 //       read when the index is seeded, a file for this backup written at its end
 //     writes out_prefix.data (the final backup data), out_prefix.meta
 //     ("iterations adds hist_seeded by_value"), out_prefix.adds (24-byte ids of
-//     Writer::add calls)
+//     Writer::add calls), out_prefix.answers (one byte per call: what add returned)
+//   ADAPTER_WRITER_ANSWERS=reference in the environment: the mock Writer
+//     returns false for an id the index already holds, as the reference's does
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -41,6 +43,11 @@ int main(int argc, char** argv) {
     fclose(sf);
   }
   ChunkStorage::Writer chunkStorageWriter;
+  const char* answers = getenv("ADAPTER_WRITER_ANSWERS");
+  if (answers && std::string(answers) == "reference") {
+    chunkStorageWriter.answerAsReference = true;
+    for (size_t i = 0; i < chunkIndex.ids.size(); ++i) chunkStorageWriter.known.insert(chunkIndex.ids[i].first.toBlob());
+  }
   try {
     GpuChunkIndex gpuIndex(config, chunkIndex, 0, ZC_FLAG_SHA1, metaDir);
     zc_stats seeded;
@@ -91,6 +98,9 @@ int main(int argc, char** argv) {
     fclose(f);
     f = fopen((p + ".adds").c_str(), "wb");
     for (size_t i = 0; i < chunkStorageWriter.ids.size(); ++i) fwrite(chunkStorageWriter.ids[i].data(), 1, 24, f);
+    fclose(f);
+    f = fopen((p + ".answers").c_str(), "wb");
+    fwrite(chunkStorageWriter.answers.data(), 1, chunkStorageWriter.answers.size(), f);
     fclose(f);
     f = fopen((p + ".meta").c_str(), "w");
     fprintf(f, "%u %zu %llu %llu\n", iterations, chunkStorageWriter.ids.size(),

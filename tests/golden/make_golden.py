@@ -1,23 +1,44 @@
 #!/usr/bin/env python3
-"""Regenerate the golden fixtures in tests/golden/ (run in the survey container,
-where /root/reference exists).
+"""Regenerate the golden fixtures in tests/golden/ (run where the reference
+sources exist).
 
-Generator: oracle/_ref/liboracle_ref.so = the restated BackupCreator state
-machine (oracle/zc_oracle.cpp) driving the reference's OWN RollingHash, compiled
-from /root/reference/rolling_hash.cc by `make -C oracle ref`.  So every rolling
-hash in these files comes from the reference's code; the boundary rules come
-from the restatement (backup_creator.cc itself cannot be built here: it needs
-the generated zbackup.pb.h and the libprotobuf runtime, which the image lacks).
+Generator: oracle/_ref/zbc_ref_cli = the reference's OWN BackupCreator and
+ChunkIndex (backup_creator.cc, chunk_index.cc, chunk_id.cc, rolling_hash.cc and
+their helpers, compiled unmodified by `make -C oracle ref` over the stand-in
+headers of oracle/refpin/), driven as zutils.cc drives them.  So the boundary
+rules, the index probe and every hash in these files come from the reference's
+code: the sequence of instructions and of Writer::add calls with their answers.
+What does not: Message::serialize and the wire encoding of the instruction
+stream (a stand-in of ours; the records are read off the calls, not off bytes),
+and the stream generator (oracle/zc_gen.cpp).
 
 `make_golden.py [OUTDIR]` writes into OUTDIR (default: this directory);
 tests/test_oracle_ref.py regenerates into a temporary directory and diffs the
 result against the committed files.
 
-Each case is a synthetic stream spec (grammar: oracle/zc_oracle.h), so the GPU
-box regenerates the exact bytes without /root/reference.  Fixture format:
-  # key: value        header (case, spec, W, seed_spec)
-  S <sha1_16> <rolling> <size>            static-index seed (ChunkIndex::loadIndex)
+Each case is a synthetic stream spec (grammar: oracle/zc_oracle.h), so a machine
+without the reference regenerates the exact bytes.  Fixture format:
+  # key: value        header (case, spec, W, n, seed_spec, feed_max, generator)
+  S <sha1_16> <rolling> <size>            index entry registered before the stream
+                                          (ChunkIndex::addChunk, in this order)
   N|D|B <offset> <size> <rolling> <sha1_16>
+  X <record index>    a NEW record whose Writer::add returned false: the id was
+                      in the index already (an earlier NEW record or a seed).
+                      Written for the rp_* cases and the corpus; the files of
+                      CASES keep their record lines only (some do hold such
+                      records, e.g. the periodic ones; tests/refpin_cases.py
+                      refused_by_ids names them from the ids)
+
+Three sets are written:
+  *.txt                 CASES below, and the directed cases of
+                        tests/refpin_cases.py (rp_*: one named edge each, fed
+                        with the recorded feed_max)
+  refpin_divergent/*.txt  the directed cases whose verdict the engine knowingly does not
+                        reproduce (tests/refpin_cases.py DIVERGENT_NAMES): held by the CPU
+                        pin, kept out of the set the GPU parity tests run
+  refbc_corpus/*.txt    100 of the fuzz streams of tests/refpin_cases.py (W <=
+                        4097, at most 40 records; those with refused adds and
+                        seeds first), several cases per file
 """
 import os
 import sys
@@ -26,6 +47,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "..", ".."))
 
 from oracle import oracle  # noqa: E402
+from tests import refpin_cases  # noqa: E402
 
 W64 = 65536
 
@@ -68,27 +90,62 @@ KAT_SPECS = [("empty", ""), ("zero65536", "Z:65536"), ("zero4464", "Z:4464"),
 
 
 def seeds_from(spec, W):
-    data = oracle.gen(spec, ref=True)
-    recs = oracle.chunk(data, W, ref=True)
+    recs, _ = oracle.chunk_refbc(oracle.gen(spec), W)
     return [(bytes.fromhex(sha), h, s) for (k, o, s, h, sha) in recs if k == "N"]
+
+
+CORPUS_N = 100
+CORPUS_PER_FILE = 10
+
+
+def corpus_cases():
+    """The recorded fuzz streams: [(index, spec, W, n, seeds, feed_max, recs, refused)]."""
+    cand = []
+    for i in range(refpin_cases.FUZZ_N):
+        spec, W, seeds, feed_max = refpin_cases.fuzz_case(i)
+        if W > 4097:
+            continue
+        data = oracle.gen(spec)
+        recs, refused = oracle.chunk_refbc(data, W, seeds, feed_max)
+        if len(recs) <= 40:
+            cand.append((i, spec, W, data.size, seeds, feed_max, recs, refused))
+    # those that say most first: refused adds, then seeded runs, then the rest
+    cand.sort(key=lambda c: (not c[7], not c[4], c[0]))
+    return sorted(cand[:CORPUS_N])
+
+
+def write_case(out_dir, name, spec, W, seeds, seed_spec=None, feed_max=None, x_lines=True):
+    data = oracle.gen(spec)
+    recs, refused = oracle.chunk_refbc(data, W, seeds, feed_max or 0)
+    # the answers follow from the ids of the records and seeds; where they are not
+    # written down (CASES) they are still checked here
+    assert refused == refpin_cases.refused_by_ids(recs, seeds), name
+    if not x_lines:
+        refused = []
+    with open(os.path.join(out_dir, f"{name}.txt"), "w") as f:
+        f.write(refpin_cases.case_text(name, spec, W, data.size, seeds, recs, refused, seed_spec, feed_max))
+    kinds = {c: sum(1 for r in recs if r[0] == c) for c in "NDB"}
+    print(f"{name:30s} n={data.size:9d} W={W:6d} records={len(recs):6d} {kinds} refused={len(refused)}")
 
 
 def main(out_dir=HERE):
     oracle.build(ref=True)
     for name, spec, W, seed_spec in CASES:
-        data = oracle.gen(spec, ref=True)
-        seeds = seeds_from(seed_spec, W) if seed_spec else []
-        recs = oracle.chunk(data, W, seeds=seeds, ref=True)
-        with open(os.path.join(out_dir, f"{name}.txt"), "w") as f:
-            f.write(f"# case: {name}\n# spec: {spec}\n# W: {W}\n# n: {data.size}\n")
-            f.write(f"# seed_spec: {seed_spec or '-'}\n")
-            f.write("# generator: oracle/_ref (restated BackupCreator + reference rolling_hash.cc)\n")
-            for sha, h, s in seeds:
-                f.write(f"S {sha.hex()} {h:016x} {s}\n")
-            for line in oracle.format_records(recs):
-                f.write(line + "\n")
-        kinds = {c: sum(1 for r in recs if r[0] == c) for c in "NDB"}
-        print(f"{name:22s} n={data.size:9d} W={W:6d} records={len(recs):6d} {kinds}")
+        write_case(out_dir, name, spec, W, seeds_from(seed_spec, W) if seed_spec else [], seed_spec, x_lines=False)
+    div_dir = os.path.join(out_dir, "refpin_divergent")
+    os.makedirs(div_dir, exist_ok=True)
+    for name, spec, W, seed_desc, feed_max in refpin_cases.DIRECTED:
+        write_case(div_dir if name in refpin_cases.DIVERGENT_NAMES else out_dir, name, spec, W,
+                   refpin_cases.build_seeds(oracle.gen(spec), W, seed_desc), feed_max=feed_max)
+    corpus_dir = os.path.join(out_dir, "refbc_corpus")
+    os.makedirs(corpus_dir, exist_ok=True)
+    corpus = corpus_cases()
+    for k in range(0, len(corpus), CORPUS_PER_FILE):
+        with open(os.path.join(corpus_dir, f"part{k // CORPUS_PER_FILE:02d}.txt"), "w") as f:
+            for i, spec, W, n, seeds, feed_max, recs, refused in corpus[k:k + CORPUS_PER_FILE]:
+                f.write(refpin_cases.case_text(f"fuzz{5000 + i}", spec, W, n, seeds, recs, refused,
+                                               feed_max=feed_max))
+    print(f"refbc_corpus: {len(corpus)} streams")
     L = oracle.lib(ref=True)
     with open(os.path.join(out_dir, "kat_digest.txt"), "w") as f:
         f.write("# RollingHash::digest(buf, size) known answers, computed by the reference's\n")

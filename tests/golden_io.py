@@ -6,7 +6,11 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def load_case(path):
-    meta, seeds, recs = {}, [], []
+    """(meta, seeds, records) of one fixture.  meta holds the header; also
+    meta["refused"], the indices of the NEW records whose Writer::add the
+    reference answered with false (the X lines; empty where the file has none),
+    and meta["feed_max"], the recorded cap on a fed piece (0: none)."""
+    meta, seeds, recs, refused = {}, [], [], []
     with open(path) as f:
         for line in f:
             line = line.rstrip("\n")
@@ -16,11 +20,15 @@ def load_case(path):
             elif line.startswith("S "):
                 _, sha, h, size = line.split()
                 seeds.append((bytes.fromhex(sha), int(h, 16), int(size)))
+            elif line.startswith("X "):
+                refused.append(int(line[2:]))
             elif line and line[0] in "NDB":
                 k, off, size, h, sha = line.split()
                 recs.append((k, int(off), int(size), int(h, 16), sha))
     meta["W"] = int(meta["W"])
     meta["n"] = int(meta["n"])
+    meta["feed_max"] = int(meta.get("feed_max", 0))
+    meta["refused"] = refused
     if meta.get("spec") is None:
         meta["spec"] = ""
     return meta, seeds, recs

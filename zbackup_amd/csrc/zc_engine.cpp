@@ -2614,6 +2614,9 @@ class Resolver {
   bool lazy_ = false;
   uint64_t r_g_ = 0;
   void abandon(uint64_t m) {
+    // (W < 128: the grid chunks are bytes_to_emit, never refs -- dead_ holds
+    // none of them; a by-value match off the grid gets here all the same)
+    if (!indexable_) return;
     for (uint32_t k = 0; k < nspec_; ++k) {
       const uint32_t g = nconf_ + k;
       if (ref_vis(g) > m && !dead_[g]) {
@@ -3410,7 +3413,11 @@ int zc_seed_index(zc_ctx* c, const zc_seed* seeds, size_t n) {
   if (!c || (n && !seeds)) return ZC_ERR_ARG;
   return guarded(c, [&] {
     for (size_t i = 0; i < n; ++i) {
-      if (seeds[i].size != c->W) continue;  // only W-byte entries can equal a W-byte window
+      // Only W-byte entries are registered, here, in zc_seed_index_meta and
+      // for the context's own chunks (hist_add / fresh_ carry W-byte chunks
+      // only): the one documented divergence from ChunkIndex::findChunk,
+      // which never reads the size (zchunk.h at zc_seed_index)
+      if (seeds[i].size != c->W) continue;
       add_static_once(*c, seeds[i].rolling, seeds[i].sha1, 1);
     }
   });
@@ -3456,7 +3463,7 @@ int zc_seed_index_meta(zc_ctx* c, const zc_seed* seeds, size_t n, const zc_chunk
     std::vector<uint64_t> fp;
     for (size_t i = 0; i < n; ++i) {
       const zc_seed& sd = seeds[i];
-      if (sd.size != W) continue;  // only W-byte entries can equal a W-byte window
+      if (sd.size != W) continue;  // only W-byte entries are registered (see zc_seed_index)
       const zc_chunk_meta* m = nullptr;
       auto it = mk.find(sd.rolling);
       if (it != mk.end())
